@@ -26,7 +26,13 @@ on more GPUs; 8: config 3's one-fold-per-GPU placement, with --train-mode full i
 ranks, value = N / wall: total work is fixed, "scaling": "strong", bounded by k / ceil(k / N) (k=5: 5 GPUs busy at N=8). The only
 exchange is the control-plane barrier / max-reduce of the timing (torch.distributed gloo, CPU tensors).
 
-The JSON line also carries
+A plain run sets up, warms up, times the sweep and prints the JSON line (metric, value, unit, ms_per_step = timed wall / steps, ...; `roofline`
+null). --dump-outputs DIR also writes what the timed sweep handed its caller (per QA pair, in id order: s(x), predicted option, correct,
+fold; per fold: first / last loss, min / max gradient norm; quantum mode: the last step's scores and context 0's loss / gradient norm) as
+DIR/<name>.npy in float64. Everything else runs only with --full: the HIP-event brackets and the clock sampler in the timed region, the
+untimed extra steps, the N = 5120 sweep (config.full_n), the config 3 child (config.full_ft) and the CPU legs (cpu_baseline).
+
+With --full the JSON line also carries
   roofline     : the dominant kernel (the projection contraction gemm_pp_kernel, 256x256 ping-pong tile): algorithmic FLOPs
                  2*M*N*(K+K2) of its launches in the timed region / the time it occupied the GPU there, measured with HIP events on the
                  launch streams; `frac` = FLOPs / WALL of the timed region (the conservative headline, checkable on the driver's clock),
@@ -223,7 +229,7 @@ def full_ft_leg(steps):
     """BASELINE config 3 measured inside the driver's run: `bench.py --train-mode full --k 8 --steps <steps>` in a child process (its own 160 GB context; the parent has
     released its contexts), reduced to the fields a reader needs. Never raises: the headline line must not be lost over this leg."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--train-mode", "full", "--k", "8", "--steps", str(steps), "--warmup", "0", "--no-cpu-baseline", "--no-full-n", "--no-full-ft"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--train-mode", "full", "--k", "8", "--steps", str(steps), "--warmup", "0", "--full", "--no-cpu-baseline", "--no-full-n", "--no-full-ft"]
     t0 = time.perf_counter()
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
@@ -239,6 +245,23 @@ def full_ft_leg(steps):
                 "note": "BASELINE config 3 on ONE GPU (the 8-GPU form puts one fold on each GPU): run in a child process behind the headline sweep, not part of `value`"}
     except Exception as e:  # noqa: BLE001
         return {"error": repr(e)}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one float64 DIR/<name>.npy per array. Should the arrays pass DUMP_MAX_BYTES (a sweep of some 26 000 steps), the longest ones are
+    cut to a fixed, seeded sample of their rows (the same rows for all of them), so that two builds still compare row for row."""
+    arrays = {name: np.asarray(a, np.float64).ravel() for name, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        n = max(len(a) for a in arrays.values())
+        keep = np.sort(np.random.default_rng(0).choice(n, int(n * DUMP_MAX_BYTES / total), replace=False))
+        arrays = {name: (a[keep] if len(a) == n else a) for name, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def sweep_layout(k, rank, world, train_mode="lora", stack=3, layout="folds"):
@@ -357,6 +380,9 @@ def main():
     ap.add_argument("--stack", type=int, default=3, help="folds STACKED per context (include/tst_hip.h: one lockstep step over the folds' concatenated "
                     "micro-batches); the resident folds are spread over ceil(folds / stack) contexts (HIP streams)")
     ap.add_argument("--tile-policy", type=int, default=-1, help="0: 128x128 contraction tiles, 1: 256x256 ping-pong tiles, 3: the same with split-K; default 1 with several streams, else 3")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: roofline (HIP events, held clock, extra untimed steps), "
+                    "config.full_n, config.full_ft, cpu_baseline; the --no-* options below switch single parts of it off")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-clock", action="store_true", help="do not sample the held shader clock during the timed sweep (roofline.clock_mhz_mean)")
     ap.add_argument("--no-full-n", action="store_true", help="do not run the extra N = 5120 sweep behind a shorter timed sweep (config.full_n)")
@@ -382,6 +408,9 @@ def main():
         cfg = dict(MODELS[args.model][1])
         print(json.dumps(cpu_baseline(cfg, D.synth_vsi(2 * TRAIN_BS, cfg["vocab_size"]), args.lora_r, args.lora_alpha, args.model, only=args.cpu_baseline_leg)))
         return
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    events = args.full and not args.no_events   # HIP-event brackets over the timed region: the roofline object (--full only)
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -526,6 +555,14 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.SUM)
         return float(tt.item())
 
+    def gather_on_rank0(items):
+        """every rank's list, concatenated on rank 0 (None elsewhere)"""
+        if dist is None:
+            return list(items)
+        parts = [None] * world if rank == 0 else None
+        dist.gather_object(list(items), parts, dst=0)
+        return [x for p in parts for x in p] if rank == 0 else None
+
     extra = {}
     if args.mode == "sweep":
         # ------------------------------------------------------------------ the metric as defined: one whole k-fold sweep
@@ -548,10 +585,10 @@ def main():
         sync_all()
         barrier()
         for c in ctxs:
-            c.profile_enable(0 if args.no_events else 1)
+            c.profile_enable(1 if events else 0)
         # the shader clock the chip HOLDS under this load, sampled every 50 ms by a one-wave probe on a stream of its own (tst_clock_probe): the 2.5 PFLOP/s
         # peak assumes 2.4 GHz, and `frac_at_held_clock` restates `frac` against the clock actually held (rank 0's GPU)
-        clock = lib.ClockSampler(local_rank).start() if (ctxs and not args.no_clock) else None
+        clock = lib.ClockSampler(local_rank).start() if (ctxs and args.full and not args.no_clock) else None
         t0 = time.perf_counter()
         records, stats = sweep(samples)          # per fold: adapter reset, one shuffled epoch (ragged last micro-batch), held-out scoring tail
         sync_all()
@@ -567,6 +604,14 @@ def main():
         sick = [st for st in stats if st.get("steps", 0) and (not st["loss_finite"] or not (st["grad_norm_min"] > 0.0))]
         if sick:
             raise SystemExit(f"fold(s) {[st['fold'] for st in sick]} did not train: loss / gradient norm non-finite or a zero gradient norm ({sick[0]})")
+        if args.dump_outputs:
+            recs, sts = gather_on_rank0(records), gather_on_rank0(stats)
+            if rank == 0:
+                recs.sort(key=lambda r: r["id"])
+                sts = sorted({st["fold"]: st for st in sts}.values(), key=lambda st: st["fold"])   # (dp-stacked: every rank reports every fold)
+                dump_outputs(args.dump_outputs, {**{key: [r[key] for r in recs] for key in ("s", "pred", "correct", "fold")},
+                                                 **{"fold_" + key: [np.nan if st.get(key) is None else st[key] for st in sts]
+                                                    for key in ("first_loss", "last_loss", "grad_norm_min", "grad_norm_max")}})
         units = n_timed
         acc = float(np.mean([r["correct"] for r in records])) if records else None
         mean_s = float(np.mean([r["s"] for r in records])) if records else None
@@ -657,7 +702,7 @@ def main():
         sync_all()
         barrier()
         for c in ctxs:
-            c.profile_enable(0 if args.no_events else 1)
+            c.profile_enable(1 if events else 0)
         t0 = time.perf_counter()
         for i in range(args.warmup, args.warmup + args.steps):
             run_step(i)
@@ -667,11 +712,16 @@ def main():
         barrier()
         units = world * F * SCORE_BS * args.steps
         loss, gnorm = ctxs[0].fetch_metrics()
+        if args.dump_outputs:
+            scored = gather_on_rank0(res)   # the last step's held-out scores, context by context, rank by rank
+            if rank == 0:
+                dump_outputs(args.dump_outputs, {"s": np.concatenate([r[0] for r in scored]), "pred": np.concatenate([r[1] for r in scored]),
+                                                 "correct": np.concatenate([r[2] for r in scored]), "loss": [loss], "grad_norm": [gnorm]})
         extra = {"qa_passes_per_s": world * F * (TRAIN_PER_STEP * TRAIN_BS + SCORE_BS) * args.steps / elapsed, "last_loss": loss, "last_grad_norm": gnorm,
                  "heldout_acc_last_batch": float(np.mean(np.concatenate([r[2] for r in res]))), "folds_on_rank0": mine}
         workload = f"k={k} TsT fold quantum loop ({TRAIN_PER_STEP}x16 QA LoRA train steps + 16 QA held-out scoring per fold and step; steady state, no fold resets), "
 
-    roof = roofline_of(ctxs, dom, policy, args, F, SK, elapsed) if (ctxs and not args.no_events) else None   # wall = MAX over ranks: conservative
+    roof = roofline_of(ctxs, dom, policy, args, F, SK, elapsed) if (ctxs and events) else None   # wall = MAX over ranks: conservative
     if roof is not None and args.mode == "sweep" and clock_mhz:
         cm = np.array(clock_mhz, np.float64)
         roof.update({"clock_mhz_mean": float(cm.mean()), "clock_mhz_min": float(cm.min()), "clock_mhz_max": float(cm.max()), "clock_samples": int(len(cm)),
@@ -681,10 +731,8 @@ def main():
     if roof is not None:
         roof.update(pmc_mfma_busy(args.model, F, SK))
 
-    if rank == 0 and args.no_events:
-        print(json.dumps({"metric": "QA-pairs/sec, full k-fold TsT on VSI-Bench text-only", "value": units / elapsed, "unit": "QA-pairs/s", "n_gpus": world,
-                          "steps": args.steps, "warmup": args.warmup, "note": "--no-events run (profiler workload): no roofline object"}))
-    elif rank == 0:
+    full_n = None
+    if rank == 0 and events:   # --full from here on (a --no-events profiler pass runs none of it)
         # one extra untimed step of context 0 alone: HBM-bound kernel classes, and the dominant kernel with the GPU to itself
         def one_step():
             smp = samples[:TRAIN_BS * SK]
@@ -711,7 +759,6 @@ def main():
         # The metric is quoted on the FULL N = 5120 set; the driver's command (--steps 20) times N = 1600. So that the driver's own
         # run also carries the quoted configuration, the full sweep runs once more here, in the same process and on the same contexts, after everything
         # the headline `value` is computed from (--no-full-n skips it; the default --steps 64 IS the full set). One GPU, LoRA sweep only.
-        full_n = None
         n_full = TRAIN_BS * k * 64
         if args.mode == "sweep" and world == 1 and args.train_mode == "lora" and not args.no_full_n and n_timed < n_full and args.model != "tiny":
             smp_full = D.synth_vsi(n_full, vocab)
@@ -731,6 +778,7 @@ def main():
                       "heldout_acc": float(np.mean([r["correct"] for r in rec_full])),
                       "note": "the same sweep over the full N = 5120 set, run once after the timed region in the same process (not part of `value`)"}
             roof["launches_after_timed_region"] += int(n_l)
+    if rank == 0:
         out = {
             "metric": "QA-pairs/sec, full k-fold TsT on VSI-Bench text-only" + (f" [dp-stacked recipe: global batch {TRAIN_BS * world}]" if layout == "dp-stacked" and world > 1 else ""),
             "value": units / elapsed,
@@ -750,9 +798,11 @@ def main():
                                        f"{SK} folds stacked per lockstep step); no data-path collective"), **extra},
             "roofline": roof,
         }
+        if args.no_events:
+            out["note"] = "--no-events run (profiler workload): no roofline object"
         # BASELINE config 3 on this GPU (Llama-3-8B FULL fine-tune, k = 8; one fold resident at a time, ~160 GB): the LoRA contexts are closed first, then a CHILD
         # process runs `bench.py --train-mode full --k 8 --steps 5` (N = 640) and its line is folded in here, so that the driver's own run carries the number
-        if (world == 1 and args.mode == "sweep" and args.train_mode == "lora" and args.model == "llama3-8b" and args.precision == "bf16" and not args.no_full_ft
+        if (events and world == 1 and args.mode == "sweep" and args.train_mode == "lora" and args.model == "llama3-8b" and args.precision == "bf16" and not args.no_full_ft
                 and not rehearsal):
             for c in reversed(ctxs):
                 c.close()
@@ -768,7 +818,7 @@ def main():
             out["vs_baseline"] = None
         if rehearsal:
             out["rehearsal"] = f"{world} ranks shared ONE GPU (TST_BENCH_SHARE_GPU=1): exercises the launch path only, the value is not a measurement"
-        if world == 1 and not args.no_cpu_baseline:
+        if events and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(cfg, samples, targs.lora_r, targs.lora_alpha, args.model)
             except Exception as e:  # the baseline is a reported side figure; never lose the GPU line over it

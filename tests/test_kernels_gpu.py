@@ -580,7 +580,8 @@ def test_embed_bwd_token_order(L, T, d, vocab, hot):
     full = np.zeros((vocab, d), np.float32)
     full[rows] = base
     dE = L.DevBuf(full)
-    assert lib.tst_k_embed_bwd(L.DevBuf(ids).ptr, L.dev_bf16(dx).ptr, dE.ptr, T, d, vocab, 0, None) == 0
+    ids_, dx_ = L.DevBuf(ids), L.dev_bf16(dx)   # held until the result is read: a temporary's buffer is freed before the launch
+    assert lib.tst_k_embed_bwd(ids_.ptr, dx_.ptr, dE.ptr, T, d, vocab, 0, None) == 0
     got = dE.get(np.float32, (vocab, d))
     np.testing.assert_array_equal(got[rows], want)
     mask = np.ones(vocab, bool)

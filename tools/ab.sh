@@ -15,7 +15,7 @@ for round in $(seq 1 $ROUNDS); do
     i=$((i+1))
     f=gpurun_out/$TAG/arm$i.r$round
     aenv="${arm%% :: *}"; aargs=""; [ "$aenv" != "$arm" ] && aargs="${arm#* :: }"
-    env $aenv timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-full-n --no-full-ft "$@" $aargs > $f.json 2> $f.err || { echo "arm '$arm' failed"; tail -5 $f.err; exit 1; }
+    env $aenv timeout -k 10 300 python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-full-n --no-full-ft "$@" $aargs > $f.json 2> $f.err || { echo "arm '$arm' failed"; tail -5 $f.err; exit 1; }
     python3 - <<PY | tee -a gpurun_out/$TAG/summary.txt
 import json
 d = json.load(open("$f.json")); r = d["roofline"]

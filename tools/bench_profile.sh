@@ -3,12 +3,13 @@
 # three roofline fractions recomputed from kernel timestamps (tools/trace_roofline.py). Summaries go to gpurun_out/<tag>/ (copy to profiles/).
 # usage: bash tools/bench_profile.sh <tag> [bench args...]
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TAG=$1; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$GRAFT_REPO_ROOT"
 echo "== bench $*"
-timeout -k 10 500 python3 bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 500 python3 bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
 python3 - <<PY
 import json
 d = json.load(open("$OUT/bench.json")); r = d["roofline"]
@@ -19,7 +20,7 @@ print("cpu", json.dumps(d.get("cpu_baseline")))
 PY
 cd /tmp && export TMPDIR=/tmp
 echo "== rocprofv3 --kernel-trace --stats (same command without the cpu baseline, the extra full-N sweep and the full fine-tune child process)"
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$GRAFT_REPO_ROOT/bench.py" "$@" --no-cpu-baseline --no-full-n --no-full-ft > "$OUT/traced_bench.json" 2> "$OUT/stats.err"
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 "$ROOT/bench.py" --full "$@" --no-cpu-baseline --no-full-n --no-full-ft > "$OUT/traced_bench.json" 2> "$OUT/stats.err"
 echo "rc=$?"
 python3 "$GRAFT_REPO_ROOT/tools/trace_roofline.py" "$OUT/stats" "$OUT/traced_bench.json" | tee "$OUT/roofline_from_trace.json"
 python3 - <<PY

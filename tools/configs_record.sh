@@ -6,13 +6,13 @@ WHICH="${*:-qwen gpt2 strict dpstacked rehearse ibp}"
 run() { n=$1; shift; echo "== $n: $*"; timeout -k 10 480 "$@" > $O/$n.json 2> $O/$n.err || { echo "$n failed"; tail -5 $O/$n.err; return; }; python3 -c "
 import json; d=json.loads(open('$O/$n.json').read().strip().splitlines()[-1]); r=d.get('roofline') or {}; print('$n', round(d['value'],2), d['unit'], 'frac', r.get('frac'), 'clock', r.get('clock_mhz_mean'))"; }
 for w in $WHICH; do case $w in
-  qwen) run qwen_k5 python3 bench.py --model qwen2.5-7b --steps 20 --warmup 5 --no-cpu-baseline --no-full-n ;;                      # config 4's base, LoRA k = 5
-  gpt2) run gpt2_k2 python3 bench.py --model gpt2-small --k 2 --steps 20 --warmup 5 --no-cpu-baseline --no-full-n ;;                # config 1's base, LoRA k = 2
-  strict) run strict_gpt2_small python3 bench.py --model gpt2-small --k 2 --precision strict --steps 10 --warmup 2 --no-cpu-baseline --no-full-n ;;
-  full) run full_k8 python3 bench.py --train-mode full --k 8 --steps 20 --warmup 0 --no-cpu-baseline ;;                             # config 3 on one GPU, N = 2560
-  dpstacked) run dpstacked_1rank python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --layout dp-stacked --steps 6 --warmup 2 --no-cpu-baseline --no-full-n ;;
+  qwen) run qwen_k5 python3 bench.py --model qwen2.5-7b --steps 20 --warmup 5 --full --no-cpu-baseline --no-full-n ;;               # config 4's base, LoRA k = 5
+  gpt2) run gpt2_k2 python3 bench.py --model gpt2-small --k 2 --steps 20 --warmup 5 --full --no-cpu-baseline --no-full-n ;;         # config 1's base, LoRA k = 2
+  strict) run strict_gpt2_small python3 bench.py --model gpt2-small --k 2 --precision strict --steps 10 --warmup 2 --full --no-cpu-baseline --no-full-n ;;
+  full) run full_k8 python3 bench.py --train-mode full --k 8 --steps 20 --warmup 0 --full --no-cpu-baseline ;;                      # config 3 on one GPU, N = 2560
+  dpstacked) run dpstacked_1rank python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --layout dp-stacked --steps 6 --warmup 2 --full --no-cpu-baseline --no-full-n ;;
   rehearse) export TST_BENCH_SHARE_GPU=1 HSA_ENABLE_IPC_MODE_LEGACY=0
-    run rehearse_n2_auto python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --steps 4 --warmup 1 --no-cpu-baseline
+    run rehearse_n2_auto python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --steps 4 --warmup 1 --full --no-cpu-baseline
     unset TST_BENCH_SHARE_GPU ;;
   ibp)  # config 5 as BASELINE states it -- 4 prune rounds x k = 5 -- at the 8B shape through the CLI (N = 800)
     PYTHONPATH=test-set-training_amd timeout -k 10 480 python3 -m tst.cli prune --model llama3-8b --n-samples 800 --k 5 --rounds 4 --num-train-epochs 1 --out $O/ibp_run > $O/config5_ibp_8b_r4_k5.log 2>&1; echo "ibp rc=$?"; tail -6 $O/config5_ibp_8b_r4_k5.log; rm -rf $O/ibp_run ;;

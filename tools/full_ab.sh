@@ -9,7 +9,7 @@ for round in $(seq 1 $ROUNDS); do
   for arm in "$@"; do
     i=$((i+1))
     f=gpurun_out/$TAG/arm$i.r$round
-    env $arm timeout -k 10 400 python3 bench.py --train-mode full --k 8 --steps $STEPS --warmup 0 --no-cpu-baseline > $f.json 2> $f.err || { echo "arm '$arm' failed"; tail -5 $f.err; exit 1; }
+    env $arm timeout -k 10 400 python3 bench.py --train-mode full --k 8 --steps $STEPS --warmup 0 --full --no-cpu-baseline > $f.json 2> $f.err || { echo "arm '$arm' failed"; tail -5 $f.err; exit 1; }
     python3 - <<PY | tee -a gpurun_out/$TAG/summary.txt
 import json
 d = json.load(open("$f.json")); r = d["roofline"]; a = r.get("hbm_kernels", {}).get("adamw", {})
