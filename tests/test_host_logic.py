@@ -29,6 +29,37 @@ def test_kfold_matches_sklearn_fixtures(golden_dir):
         kfold.kfold_assign(3, 5)
 
 
+def test_planned_maxlen_around_the_128_token_kernel_switch():
+    """plan_batch's maxlen picks the attention kernel family (<= 128: shared-staging kernels and RoPE inside them; above: the general kernels and
+    the stand-alone rope kernel). With trim_last the last token of EVERY sequence is dropped -- it predicts nothing and, under the causal mask, nothing
+    attends to it -- so a 129-token sequence plans 128 whether or not it carries labels, and 129 with trim off. Caller-chosen rows
+    (tst_forward_logits) may read any position: the sequence is kept whole, as is a one-token sequence."""
+    import golden_inputs as GI
+    from tst import lib
+    rng = np.random.default_rng(129)
+    mc = lib.make_model_cfg(GI.TINY_CFG, max_tokens=512, max_seqs=8, max_labelled=64, max_position=256)
+    lengths = (129, 40, 1, 7)
+    cu = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+    ids = rng.integers(0, GI.TINY_CFG["vocab_size"], int(cu[-1])).astype(np.int32)
+    for labelled_129 in (True, False):
+        labels = np.full(len(ids), -100, np.int32)
+        labels[cu[2] - 3:cu[2]] = ids[cu[2] - 3:cu[2]]            # the 40-token sequence is labelled in both cases
+        if labelled_129:
+            labels[cu[1] - 1] = ids[cu[1] - 1]                    # the 129-token sequence: its last token
+        whole = lib.host_plan_batch(mc, ids, labels, cu, trim_last=False)
+        assert whole["maxlen"] == 129 and list(np.diff(whole["cu"])) == list(lengths)
+        trimmed = lib.host_plan_batch(mc, ids, labels, cu, trim_last=True)
+        assert trimmed["maxlen"] == 128, (labelled_129, trimmed["maxlen"])
+        assert list(np.diff(trimmed["cu"])) == [128, 39, 1, 6]
+        assert trimmed["R"] == whole["R"] == 3 + int(labelled_129)
+        # the labelled rows point at the same source positions either way (trimming only drops the tail of each sequence)
+        src = lambda p: np.searchsorted(p["cu"], p["lab_idx"], side="right") - 1
+        np.testing.assert_array_equal(src(trimmed), src(whole))
+        np.testing.assert_array_equal(trimmed["targets"], whole["targets"])
+        rows = lib.host_plan_batch(mc, ids, labels, cu, trim_last=True, rows=[int(cu[1]) - 1, 0])
+        assert rows["maxlen"] == 129
+
+
 def test_fold_placement():
     from tst import kfold
     assert [kfold.folds_for_rank(5, r, 8) for r in range(8)] == [[0], [1], [2], [3], [4], [], [], []]

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import golden_inputs as GI
 from oracle import ops_np as O
 
 pytestmark = pytest.mark.gpu
@@ -608,6 +609,44 @@ def test_rope(L):
     assert lib.tst_k_rope(d_.ptr, p_.ptr, c_.ptr, s_.ptr, T, H + Hkv, dh, ld, 1) == 0
     back = O.rope_apply(rot, cos[pos], sin[pos], bf16=True, backward=True).reshape(T, -1)
     assert_close("rope_bwd", d_.get_bf16((T, ld))[:, : (H + Hkv) * dh], back, BF_ULP, 1e-3)
+
+
+@pytest.mark.parametrize("tag", ["llama31", "linear4", "theta500k"])
+@pytest.mark.parametrize("precision", ["bf16", "f32"])
+def test_rope_long_positions(L, tag, precision):
+    """the stand-alone rope kernel (sequences over 128 tokens: engine.hip runs it around attention) at positions spread over 0 .. 8191, on tables
+    of a Llama-3.1 scaled, a linearly scaled and a plain theta = 500000 frequency set; forward, then backward back to the input. bf16: the bound of
+    test_rope; fp32: summation-free, so within a few fp32 ulps. v untouched either way."""
+    rng = np.random.default_rng(8191 + len(tag))
+    T, H, Hkv, dh, P = 300, 4, 2, 128, 8192
+    ld = (H + 2 * Hkv) * dh
+    nrot = (H + Hkv) * dh
+    theta, rs = {c[0]: c[1:] for c in GI.ROPE_SCALING_CASES}.get(tag, (500000.0, None))
+    bf = precision == "bf16"
+    cos, sin = O.rope_tables(np.arange(P), dh, theta, bf16=bf, scaling=rs)
+    pos = rng.integers(0, P, T).astype(np.int32)
+    pos[:4] = (0, 1, P - 2, P - 1)
+    qkv = rng.standard_normal((T, ld)).astype(np.float32)
+    if bf:
+        qkv = O.rbf(qkv)
+    lib = L.load_lab()
+    d_ = L.dev_bf16(qkv) if bf else L.dev_f32(qkv)
+    p_, c_, s_ = L.DevBuf(pos), L.DevBuf(cos), L.DevBuf(sin)
+    get = (lambda: d_.get_bf16((T, ld))) if bf else (lambda: d_.get(np.float32, (T, ld)))
+    rope = lib.tst_k_rope if bf else lib.tst_k_rope_f32
+    rtol, atol = (BF_ULP, 1e-3) if bf else (1e-6, 1e-6)
+    assert rope(d_.ptr, p_.ptr, c_.ptr, s_.ptr, T, H + Hkv, dh, ld, 0) == 0
+    fwd = get()
+    rot = O.rope_apply(qkv[:, :nrot].reshape(T, H + Hkv, dh), cos[pos], sin[pos], bf16=bf)
+    assert_close(f"rope_fwd long {tag} {precision}", fwd[:, :nrot], rot.reshape(T, -1), rtol, atol)
+    np.testing.assert_array_equal(fwd[:, nrot:], qkv[:, nrot:])
+    assert rope(d_.ptr, p_.ptr, c_.ptr, s_.ptr, T, H + Hkv, dh, ld, 1) == 0
+    got = get()
+    back = O.rope_apply(fwd[:, :nrot].reshape(T, H + Hkv, dh), cos[pos], sin[pos], bf16=bf, backward=True)
+    assert_close(f"rope_bwd long {tag} {precision}", got[:, :nrot], back.reshape(T, -1), rtol, atol)
+    if not bf:   # fp32 tables: cos^2 + sin^2 = 1 to fp32 precision, so the backward undoes the forward (bf16 tables are off by up to 2^-8)
+        assert_close(f"rope_roundtrip long {tag} {precision}", got[:, :nrot], qkv[:, :nrot], 2 * rtol, 2 * atol)
+    np.testing.assert_array_equal(got[:, nrot:], qkv[:, nrot:])
 
 
 def test_swiglu(L):

@@ -135,6 +135,55 @@ def test_attention_f32(L, lengths, H, Hkv, dh):
     chk("dv", dqkv[:, (H + Hkv) * dh:].reshape(T, Hkv, dh), dv_ref, 5e-5)
 
 
+@pytest.mark.parametrize("lengths,H,Hkv,dh", [((1, 7, 129, 64, 300, 65), 4, 1, 128), ((1, 7, 129, 64, 300, 65), 7, 1, 128), ((1, 7, 129, 64, 300, 65), 12, 12, 64),
+                                             ((191, 192, 193), 8, 2, 128), ((255, 256, 257), 8, 2, 128), ((2048,), 4, 1, 128)])
+@pytest.mark.parametrize("planted", [False, True])
+def test_attention_f32_long_sequences(L, lengths, H, Hkv, dh, planted):
+    """attn_f32.hip on batches whose longest sequence has more than 128 tokens -- several sequences, tile edges past 128, 2048 tokens -- against
+    float64 attention. Every output is poisoned before its launch.
+    planted=False: unit-scale inputs, the bounds of test_attention_f32 (out 2e-5, lse 2e-6, gradients 5e-5 of rms).
+    planted=True: the extremes of tests/test_attention_long_gpu.py (a row maximum in the last key tile, a dominant key in tile 0, one head whose
+    scores reach ~50 and beyond). Out and gradients then get twice the bound: a score S carries an fp32 rounding of ~|S| 2^-24 into P = exp(S - lse)
+    as a RELATIVE error, so scores 10x larger than unit scale give proportionally larger output errors. That is not growth with n: measured out 1.75e-5
+    at 300 tokens, 2.2e-5 at 191 - 257 and 2.5e-5 at 2048 (a summation term would grow ~sqrt(7) = 2.6x from 300 to 2048, a tile defect far more), dk
+    5.2e-5 at 300 tokens. lse keeps its bound.
+    dK, which sums G x n terms for the first keys of a sequence, is the one output whose error grows with n: measured max|d|/rms 7.3e-6 at 130 tokens,
+    2.0e-5 at 300 and 1.12e-4 at 2048, i.e. n 2^-24 at every length -- the worst-case (linear) form of fp32 summation error rather than the random-walk
+    sqrt(n) form, and nowhere near a tile defect (which would show as errors of order 1e-3 at tile boundaries). Gradients are therefore held to
+    max(5e-5, 1.5 n 2^-24) with n the longest sequence; the linear growth itself is left for a follow-up look at the dK accumulation order."""
+    from test_attention_long_gpu import POISON, exact_attention_bwd, exact_attention_fwd, make_inputs, split
+    T = sum(lengths)
+    qkv, do, cu = make_inputs(lengths, H, Hkv, dh, seed=T + 7 * H + dh, plant=planted)
+    widen = 2.0 if planted else 1.0
+    gtol = max(5e-5, 1.5 * max(lengths) * 2.0 ** -24) * widen
+    q, k, v = split(qkv, T, H, Hkv, dh)
+    out_ref, lse_ref = exact_attention_fwd(q, k, v, cu)
+    dq_ref, dk_ref, dv_ref = exact_attention_bwd(q, k, v, do.reshape(T, H, dh), cu)
+    ld = qkv.shape[1]
+    lib = L.load_lab()
+    qkv_, cu_, do_ = L.dev_f32(qkv), L.DevBuf(cu), L.dev_f32(do)
+    out_, lse_, delta_, dqkv_ = L.DevBuf(nbytes=T * H * dh * 4), L.DevBuf(nbytes=H * T * 4), L.DevBuf(nbytes=H * T * 4), L.DevBuf(nbytes=T * ld * 4)
+    for buf in (out_, lse_, delta_, dqkv_):
+        assert lib.tst_dev_memset(buf.ptr, POISON, buf.nbytes) == 0
+    scale = 1.0 / np.sqrt(dh)
+    assert lib.tst_k_attn_fwd_f32(qkv_.ptr, ld, cu_.ptr, len(lengths), max(lengths), out_.ptr, H * dh, lse_.ptr, T, H, Hkv, dh, scale) == 0
+    assert lib.tst_k_attn_bwd_f32(qkv_.ptr, ld, out_.ptr, H * dh, do_.ptr, H * dh, lse_.ptr, delta_.ptr, cu_.ptr, len(lengths), max(lengths), dqkv_.ptr, T,
+                                  H, Hkv, dh, scale) == 0
+    tag = f"long{' planted' if planted else ''} L{'_'.join(map(str, lengths))} H{H}/{Hkv} dh{dh}"
+    dqkv = dqkv_.get(np.float32, (T, ld))
+    dq, dk, dv = split(dqkv, T, H, Hkv, dh)
+
+    def chk(name, a, b, tol):
+        e = float(np.abs(a - b).max() / (np.sqrt(np.mean(b.astype(np.float64) ** 2)) + 1e-30))
+        report(f"attn_f32 {name} {tag} vs fp64: max|d|/rms = {e:.2e}")
+        assert np.isfinite(a).all() and e <= tol, (name, e)
+    chk("out", out_.get(np.float32, (T, H, dh)), out_ref, 2e-5 * widen)
+    chk("lse", lse_.get(np.float32, (H, T)), lse_ref, 2e-6)
+    chk("dq", dq, dq_ref, gtol)
+    chk("dk", dk, dk_ref, gtol)
+    chk("dv", dv, dv_ref, gtol)
+
+
 def test_attention_f32_matches_hf_fixture(L, golden_dir):
     """HF eager_attention_forward (fp32) fixture: forward output and all three gradients, to fp32 summation order."""
     g = np.load(os.path.join(golden_dir, "ops.npz"))
