@@ -105,15 +105,6 @@ int tst_k_gemm_bench(const void* A, const void* B, void* C, int M, int N, int K,
 int tst_k_gemm_bench_masked(const void* A, const void* B, void* C, int M, int N, int K, int out_f32, int variant, int splitk, int iters, int mask_width, int nslot,
                             float* ms_out);
 
-
-/* gate|up projection with SwiGLU in the epilogue: gu[M, N] = A[M,K].B[N,K]^T with gate / up interleaved in blocks of 128 columns,
- * act[M, N/2] = silu(gate) * up. variant 5: the fused 256x256 tile; other variants: contraction, then the elementwise kernel. */
-int tst_k_gemm_swiglu_fwd(const void* A, int64_t lda, const void* B, int64_t ldb, void* gu, void* act, int M, int N, int K, int variant);
-/* dX of the down projection with SwiGLU backward in the epilogue: d(act)[M, F] = dy[M,K].WT[F,K]^T is not stored (dact_scratch is used
- * by the unfused variants only); dgu[M, 2F] = d(gate|up) from gu[M, 2F], both interleaved. */
-int tst_k_gemm_swiglu_bwd(const void* dy, int64_t lda, const void* WT, int64_t ldb, const void* gu, void* dgu, void* dact_scratch, int M, int F, int K,
-                          int variant);
-
 /* ---- fp32 "strict" kernels (csrc/gemm_f32.hip, csrc/attn_f32.hip): the same contracts on fp32 tensors ---- */
 /* C[M,N] (fp32) = alpha*(A[M,K].B[N,K]^T + A2[M,K2].B2[N,K2]^T) (+R) (+bias[N]); every operand fp32 */
 int tst_k_gemm_f32_nt(const void* A, int64_t lda, const void* B, int64_t ldb, const void* A2, int64_t lda2, const void* B2, int64_t ldb2, void* C,

@@ -389,36 +389,30 @@ __global__ __launch_bounds__(256) void rope_kernel(AT* __restrict__ qkv, const i
 }
 
 // ---------------- K5 SwiGLU: modeling_llama.py:175, activations.py (silu) ----------------
-// column of gate value c (0 <= c < F) inside a [.., 2F] row; the up value sits up_off(F, il) further
-__device__ __forceinline__ int gate_col(int c, int il) { return il ? (c / il) * 2 * il + c % il : c; }
-__device__ __forceinline__ int up_off(int F, int il) { return il ? il : F; }
-
 // grid (column chunks of 256 x 8 elements, row slices): a thread keeps its 8 columns and walks rows blockIdx.y, + gridDim.y, ... -- no index division (the flat
 // 64-bit i / c8n, i % c8n of the first form cost more VALU instructions than the arithmetic, which is what these kernels are short of beside the projection
 // tiles of the other stream)
 template <typename AT>
-__global__ __launch_bounds__(256) void swiglu_fwd_kernel(const AT* __restrict__ gu, AT* __restrict__ act, int T, int F, int il) {
+__global__ __launch_bounds__(256) void swiglu_fwd_kernel(const AT* __restrict__ gu, AT* __restrict__ act, int T, int F) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= (F >> 3)) return;
-  const int gc = gate_col(c * 8, il), uo = up_off(F, il);
   for (int t = blockIdx.y; t < T; t += gridDim.y) {
     float g[8], u[8];
-    ld8(gu + (long)t * 2 * F + gc, g);
-    ld8(gu + (long)t * 2 * F + gc + uo, u);
+    ld8(gu + (long)t * 2 * F + c * 8, g);
+    ld8(gu + (long)t * 2 * F + F + c * 8, u);
 #pragma unroll
     for (int j = 0; j < 8; ++j) g[j] = swiglu_of<AT>(g[j], u[j]);
     st8(act + (long)t * F + c * 8, g);
   }
 }
 template <typename AT>
-__global__ __launch_bounds__(256) void swiglu_bwd_kernel(const AT* __restrict__ dact, const AT* __restrict__ gu, AT* __restrict__ dgu, int T, int F, int il) {
+__global__ __launch_bounds__(256) void swiglu_bwd_kernel(const AT* __restrict__ dact, const AT* __restrict__ gu, AT* __restrict__ dgu, int T, int F) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= (F >> 3)) return;
-  const int gc = gate_col(c * 8, il), uo = up_off(F, il);
   for (int t = blockIdx.y; t < T; t += gridDim.y) {
     float g[8], u[8], da[8], dg[8], du[8];
-    ld8(gu + (long)t * 2 * F + gc, g);
-    ld8(gu + (long)t * 2 * F + gc + uo, u);
+    ld8(gu + (long)t * 2 * F + c * 8, g);
+    ld8(gu + (long)t * 2 * F + F + c * 8, u);
     ld8(dact + (long)t * F + c * 8, da);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -426,8 +420,8 @@ __global__ __launch_bounds__(256) void swiglu_bwd_kernel(const AT* __restrict__ 
       dg[j] = da[j] * u[j] * sg * (1.0f + g[j] * (1.0f - sg));
       du[j] = da[j] * g[j] * sg;
     }
-    st8(dgu + (long)t * 2 * F + gc, dg);
-    st8(dgu + (long)t * 2 * F + gc + uo, du);
+    st8(dgu + (long)t * 2 * F + c * 8, dg);
+    st8(dgu + (long)t * 2 * F + F + c * 8, du);
   }
 }
 
@@ -785,16 +779,16 @@ static dim3 swiglu_grid(int T, int F) {
   if (gy > T) gy = T;
   return dim3(gx, gy);
 }
-template <typename AT> int swiglu_fwd(hipStream_t st, const AT* gu, AT* act, int T, int F, int il) {
-  if ((F & 7) || (il && ((il & 7) || F % il))) return TST_EINVAL;
+template <typename AT> int swiglu_fwd(hipStream_t st, const AT* gu, AT* act, int T, int F) {
+  if (F & 7) return TST_EINVAL;
   if (T <= 0) return TST_OK;
-  hipLaunchKernelGGL(swiglu_fwd_kernel<AT>, swiglu_grid(T, F), dim3(256), 0, st, gu, act, T, F, il);
+  hipLaunchKernelGGL(swiglu_fwd_kernel<AT>, swiglu_grid(T, F), dim3(256), 0, st, gu, act, T, F);
   return CHECK_LAUNCH();
 }
-template <typename AT> int swiglu_bwd(hipStream_t st, const AT* dact, const AT* gu, AT* dgu, int T, int F, int il) {
-  if ((F & 7) || (il && ((il & 7) || F % il))) return TST_EINVAL;
+template <typename AT> int swiglu_bwd(hipStream_t st, const AT* dact, const AT* gu, AT* dgu, int T, int F) {
+  if (F & 7) return TST_EINVAL;
   if (T <= 0) return TST_OK;
-  hipLaunchKernelGGL(swiglu_bwd_kernel<AT>, swiglu_grid(T, F), dim3(256), 0, st, dact, gu, dgu, T, F, il);
+  hipLaunchKernelGGL(swiglu_bwd_kernel<AT>, swiglu_grid(T, F), dim3(256), 0, st, dact, gu, dgu, T, F);
   return CHECK_LAUNCH();
 }
 template <typename AT> int logit_rows(hipStream_t st, const float* logits, long ld, const int* target, int n_rows, int V, float* stats, AT* dlogits, long ldd,
@@ -877,8 +871,8 @@ template <typename AT> int fill_const(hipStream_t st, AT* out, long n, float v) 
   template int gelu_bwd<AT>(hipStream_t, const AT*, const AT*, AT*, long);                                                                  \
   template int embed_pos_fwd<AT>(hipStream_t, const int*, const int*, const AT*, const AT*, AT*, int, int, int, int);                       \
   template int rope_apply<AT>(hipStream_t, AT*, const int*, const float*, const float*, int, int, int, long, int);                          \
-  template int swiglu_fwd<AT>(hipStream_t, const AT*, AT*, int, int, int);                                                                       \
-  template int swiglu_bwd<AT>(hipStream_t, const AT*, const AT*, AT*, int, int, int);                                                            \
+  template int swiglu_fwd<AT>(hipStream_t, const AT*, AT*, int, int);                                                                       \
+  template int swiglu_bwd<AT>(hipStream_t, const AT*, const AT*, AT*, int, int);                                                            \
   template int logit_rows<AT>(hipStream_t, const float*, long, const int*, int, int, float*, AT*, long, float, const int*, int, float*);    \
   template int cast_from_f32<AT>(hipStream_t, const float*, AT*, long, float);                                                              \
   template int randn_fill<AT>(hipStream_t, AT*, long, unsigned, float);                                                                     \

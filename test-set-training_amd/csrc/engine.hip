@@ -197,14 +197,7 @@ struct tst_ctx {
   size_t opt_joined = 0;            // events of the pending optimizer step the context's stream already waits for
   bool opt_pending = false;
   bool opt_overlap = env_flag("TST_OPT_OVERLAP", true);   // "opt_overlap" (tst_set_option)
-  // TST_OPT_FWD_TILES=1 (A/B switch, default off): a forward that starts while an optimizer step is pending runs its projections on the 128 x 128 tiles
-  // (72 VGPRs, 4 waves, 64 KB of LDS: such a workgroup fits on a CU BESIDE AdamW's waves, the 256 x 256 tile needs an empty CU). Measured slower:
-  // the pair is bound by HBM in aggregate, not by CU placement (profiles/r04_full_overlap_ab.txt).
-  bool fwd_small_tiles = false;
   bool gpt2 = false;
-  bool fuse_sw_fwd = false, fuse_sw_bwd = false;   // TST_FUSE_SWIGLU = 1: both epilogues, 2: the forward one only, 3: the backward one only (gu_il is 128 for all three)
-  int gu_il = 0;   // 128: gate and up rows of Wgu (and the columns of gu / dgu) are interleaved in blocks of 128 so that one 256-column tile of the
-                   // gate|up projection holds matching gate and up columns: SwiGLU runs in the contraction epilogues (LoRA, bf16 path); 0: [gate | up]
   int Vp = 0;    // vocabulary padded to a multiple of 64 (GPT-2: 50257 -> 50304): row count of embed / lm_head, ld of the logits
   int Fgu = 0;   // output width of the first MLP projection: 2F (gate|up) or F (c_fc)
   int npos = 0;  // rows of wpe
@@ -288,7 +281,6 @@ struct tst_ctx {
   bool ndw_open[2] = {false, false};
   hipEvent_t ev_ndw[2] = {nullptr, nullptr};
   float* colred_ws_side = nullptr;
-  bool tns_side_open = false;  // (TST_TNS_SIDE) the layer's adapter-gradient launch is in flight on the side stream
   bool in_backward = false;    // (between the entry and the exit of backward(): the tile policy of a full fine-tune may differ by pass)
   bool dw_side_open = false;   // full fine-tune: weight-gradient work of the current layer is in flight on the side stream (joined per layer)
   float* side_slab = nullptr;
@@ -538,8 +530,7 @@ int run_gemm(CtxT<AT>* ctx, GemmParamsT<AT> p, bool on_side = false) {
     static const int fsk = [] { const char* e = getenv("TST_FULL_SPLITK"); return e ? atoi(e) : 2; }();   // A/B: bit 0 = split-K in the forward (under AdamW the slabs add HBM traffic to the saturated side), bit 1 = in the backward; 2: profiles/r05_full_splitk_ab.txt
     if (!(fsk & (ctx->in_backward ? 2 : 1))) p.no_splitk = 1;
   }
-  int rc = gemm_nt(gst, p, on_side ? ctx->side_slab : ctx->slab, on_side ? ctx->side_slab_bytes : ctx->slab_bytes,
-                   (sizeof(AT) == 2 && ctx->fwd_small_tiles && p.N > 512 && !p.out_f32) ? 0 : -1, -1, used);
+  int rc = gemm_nt(gst, p, on_side ? ctx->side_slab : ctx->slab, on_side ? ctx->side_slab_bytes : ctx->slab_bytes, -1, -1, used);
   ctx->last_variant = used[0]; ctx->last_sk = used[1];
   double flop = 2.0 * p.M * p.N * (double)(p.K + p.K2);
   if (p.k2_w > 0 && used[0] == 5 && used[1] == 1) {   // the ping-pong tile ran only the K2 k-tiles of its rows' slots: count what ran
@@ -606,7 +597,7 @@ template <typename AT>
 bool swr_setup(CtxT<AT>* ctx, const LoraGroupT<AT>& g, bool backward, int T, AT* C, SwiRank& r) {
   if constexpr (sizeof(AT) != 2) return false;
   else {
-    if (!(ctx->swr & (backward ? 2 : 1)) || ctx->gpt2 || ctx->full || !g.on || ctx->gu_il != 0 || whatif()) return false;
+    if (!(ctx->swr & (backward ? 2 : 1)) || ctx->gpt2 || ctx->full || !g.on || whatif()) return false;
     memset(&r, 0, sizeof(r));
     r.B = backward ? g.d.BgT : g.d.Ag; r.ldb = backward ? 2L * ctx->F : (long)ctx->F; r.C = C; r.N = g.d.RP;
     r.alpha = backward ? 1.0f : g.d.scale;
@@ -617,13 +608,13 @@ bool swr_setup(CtxT<AT>* ctx, const LoraGroupT<AT>& g, bool backward, int T, AT*
     // gate|up group: module 0 owns the gate rows, module 1 the up rows -- Bg is block diagonal, half of BgT's entries in a slot's rank block are zeros by construction
     r.block_diag = backward && r.mask_width && g.d.nmod == 2 && g.d.seg_row0[0] == 0 && g.d.seg_row1[0] == ctx->F && g.d.seg_row0[1] == ctx->F &&
                    g.d.seg_row1[1] == 2 * ctx->F;
-    return swiglu_rank_supported(T, ctx->F, ctx->gu_il, r);
+    return swiglu_rank_supported(T, ctx->F, r);
   }
 }
 
 template <typename AT>
 int linear_fwd(CtxT<AT>* ctx, const AT* x, int din, const AT* W, int dout, const LoraGroupT<AT>& g, AT* us, const AT* R, AT* y, int T,
-               const AT* bias = nullptr, AT* act_out = nullptr, bool us_done = false) {
+               const AT* bias = nullptr, bool us_done = false) {
   if (g.on && !us_done) {   // us_done: the kernel that produced x has formed us = s x . Ag^T on the way (swiglu_rank_fwd)
     GemmParamsT<AT> q = gp<AT>(x, din, g.d.Ag, din, us, g.d.RP, T, g.d.RP, din);
     q.alpha = g.d.scale;
@@ -634,7 +625,6 @@ int linear_fwd(CtxT<AT>* ctx, const AT* x, int din, const AT* W, int dout, const
   if (g.on) { p.A2 = us; p.lda2 = g.d.RP; p.B2 = g.d.Bg; p.ldb2 = g.d.RP; p.K2 = g.d.RP; k2_slots(ctx, p, g.d.nmod * g.d.r); }
   p.R = R; p.ldr = dout;
   p.bias = bias;
-  if (act_out) { p.act_out = act_out; p.il = ctx->gu_il; }   // gate|up projection: act = silu(gate) * up in the epilogue (or right behind it)
   return run_gemm(ctx, p);
 }
 
@@ -654,10 +644,8 @@ AT* du_target(CtxT<AT>* ctx, const LoraGroupT<AT>& g, int slot, bool* grouped_ou
 }
 
 template <typename AT>
-int flush_tn(CtxT<AT>* ctx, bool on_side);
-template <typename AT>
 int linear_bwd(CtxT<AT>* ctx, const AT* dy, int dout, const AT* x, int din, const AT* W, const AT* WT, const LoraGroupT<AT>& g, const AT* us, AT* dx, int T,
-               float* dW = nullptr, int slot = 0, const AT* sw_gu = nullptr, AT* sw_dgu = nullptr, bool need_dx = true, bool du_done = false) {
+               float* dW = nullptr, int slot = 0, bool need_dx = true, bool du_done = false) {
   // full fine-tune: dW[dout,din] = dy^T . x (fp32, written straight into the flat gradient buffer). Both factors are large and the contraction axis
   // (tokens) is short. Round 5: the TN member of the 256x256 ping-pong tile contracts the row-major activations as they are (rows >= T of the last k-tile
   // are out of range of its buffer descriptor and read as zeros). Before (ctx->kmajor bit 1 off, strict mode): both activations transposed into zero-padded
@@ -684,8 +672,6 @@ int linear_bwd(CtxT<AT>* ctx, const AT* dy, int dout, const AT* x, int din, cons
       if ((ctx->kmajor & 2) && T > 256) {
         GemmParams w = gp<AT>(dy, dout, x, din, dW, din, dout, din, roundup(T, 64));
         w.ta = 1; w.tb = 1; w.kvalid = T; w.out_f32 = 1; w.sumsq = ssq; w.no_tail = 1;
-        static const bool dw_nt = env_flag("TST_DW_NT", false);   // A/B switch: neutral on config 3 (24.38 vs 24.38 QA/s, profiles/r05_full_dw_nt_ab.txt), off
-        w.nt_out = dw_nt ? 1 : 0;
         if (gemm_pp_kmajor_supported(w)) {
           const int pslot = prof_begin(ctx, wst, ctx->prof);
           int used[2] = {5, 1};
@@ -760,10 +746,6 @@ int linear_bwd(CtxT<AT>* ctx, const AT* dy, int dout, const AT* x, int din, cons
       CTX_RC(run_gemm_tn<AT>(ctx, du, RP, x, din, g.d.dAg, din, RP, din, T, g.d.scale, on_side));
     }
   }
-  if (slot == 3 && need_dx && !ctx->lc_active) {   // TST_TNS_SIDE=1 (A/B switch): the layer's adapter-gradient launch on the side stream, beside the contraction below
-    static const bool tns_side = env_flag("TST_TNS_SIDE", false);
-    if (tns_side && !ctx->full && ctx->ns > 1) CTX_RC(flush_tn(ctx, true));
-  }
   if (!need_dx) return TST_OK;   // (the first layer of a LoRA fine-tune: nothing trainable lies below its q|k|v projection)
   if constexpr (sizeof(AT) == 2) {
     if (!WT) {   // full fine-tune without W^T copies (ctx->kmajor bit 0): dx = dy . W on the NN member, W[dout][din] as it is stored
@@ -781,7 +763,6 @@ int linear_bwd(CtxT<AT>* ctx, const AT* dy, int dout, const AT* x, int din, cons
   }
   GemmParamsT<AT> p = gp<AT>(dy, dout, WT, dout, dx, din, T, din, dout);
   if (g.on) { p.A2 = du; p.lda2 = g.d.RP; p.B2 = g.d.AgT; p.ldb2 = g.d.RP; p.K2 = g.d.RP; k2_slots(ctx, p, g.d.nmod * g.d.r); }
-  if (sw_dgu) { p.sw_gu = sw_gu; p.sw_dgu = sw_dgu; p.il = ctx->gu_il; }   // dX of the down projection feeds SwiGLU backward: d(gate|up) from the epilogue
   return run_gemm(ctx, p);
 }
 
@@ -935,8 +916,6 @@ int forward(CtxT<AT>* ctx, bool stash) {
   ctx->lc_used = ctx->lc_on && ctx->lc_batch_ok && ctx->cur_R > 0 && 2 * ctx->cur_R <= T;
   ctx->lc_active = false;
   whatif_tick();   // (process-wide: the bench's contexts step in turn)
-  static const bool small_env = env_flag("TST_OPT_FWD_TILES", false);
-  ctx->fwd_small_tiles = small_env && ctx->opt_pending;   // (cleared by head_forward, which joins the optimizer)
   CTX_RC(opt_need(ctx, 1));   // norm vectors / biases and the embedding side of a pending optimizer step
   if (ctx->gpt2) CTX_RC(embed_pos_fwd<AT>(st, ctx->d_ids, ctx->d_pos, ctx->embed, ctx->wpe, L0.x_in, T, d, ctx->V, ctx->npos));
   else CTX_RC(embed_fwd<AT>(st, ctx->d_ids, ctx->embed, L0.x_in, T, d, ctx->V));
@@ -953,7 +932,7 @@ int forward(CtxT<AT>* ctx, bool stash) {
       CTX_RC(nrc);
     }
     if (!u_qkv && !(whatif() & 1)) CTX_RC(norm_fwd<AT>(ctx, x_in, W.attn_norm, W.attn_norm_b, A.xn1, A.rstd1, T));
-    CTX_RC(linear_fwd<AT>(ctx, A.xn1, d, W.Wqkv, ctx->dqkv, W.g_qkv, A.us_qkv, nullptr, A.qkv, T, W.bqkv, nullptr, u_qkv));
+    CTX_RC(linear_fwd<AT>(ctx, A.xn1, d, W.Wqkv, ctx->dqkv, W.g_qkv, A.us_qkv, nullptr, A.qkv, T, W.bqkv, u_qkv));
     // RoPE: inside the attention kernels where they can (bf16 path, sequences <= 128 tokens: q and k then stay UN-rotated in the stash and
     // the backward kernel rotates dq / dk back itself), else as a pass of its own over q and k
     const bool rope_in = !ctx->gpt2 && rope_fused(ctx);
@@ -977,18 +956,17 @@ int forward(CtxT<AT>* ctx, bool stash) {
       ctx->lc_active = true;
       int rc = linear_fwd<AT>(ctx, ctx->lc_attn, ctx->dattn, W.Wo, d, W.g_o, ctx->lc_us_o, ctx->lc_xin, ctx->lc_hmid, R, W.bo);
       if (rc == TST_OK) rc = norm_fwd<AT>(ctx, ctx->lc_hmid, W.mlp_norm, W.mlp_norm_b, ctx->lc_xn2, ctx->lc_rstd2, R);
-      if (rc == TST_OK) rc = linear_fwd<AT>(ctx, ctx->lc_xn2, d, W.Wgu, ctx->Fgu, W.g_gu, ctx->lc_us_gu, nullptr, ctx->lc_gu, R, W.bgu, ctx->fuse_sw_fwd ? ctx->lc_act : nullptr);
+      if (rc == TST_OK) rc = linear_fwd<AT>(ctx, ctx->lc_xn2, d, W.Wgu, ctx->Fgu, W.g_gu, ctx->lc_us_gu, nullptr, ctx->lc_gu, R, W.bgu);
       bool us_done = false;
       if (rc == TST_OK) {
         SwiRank sr;
         if (ctx->gpt2) rc = gelu_fwd<AT>(st, ctx->lc_gu, ctx->lc_act, (long)R * ctx->F);
-        else if (ctx->fuse_sw_fwd) {
-        } else if (swr_setup<AT>(ctx, W.g_d, false, R, ctx->lc_us_d, sr)) {
+        else if (swr_setup<AT>(ctx, W.g_d, false, R, ctx->lc_us_d, sr)) {
           if constexpr (sizeof(AT) == 2) rc = swiglu_rank_fwd(st, ctx->lc_gu, ctx->lc_act, R, ctx->F, sr);
           us_done = true;
-        } else rc = swiglu_fwd<AT>(st, ctx->lc_gu, ctx->lc_act, R, ctx->F, ctx->gu_il);
+        } else rc = swiglu_fwd<AT>(st, ctx->lc_gu, ctx->lc_act, R, ctx->F);
       }
-      if (rc == TST_OK) rc = linear_fwd<AT>(ctx, ctx->lc_act, ctx->F, W.Wd, d, W.g_d, ctx->lc_us_d, ctx->lc_hmid, ctx->xg, R, W.bd, nullptr, us_done);
+      if (rc == TST_OK) rc = linear_fwd<AT>(ctx, ctx->lc_act, ctx->F, W.Wd, d, W.g_d, ctx->lc_us_d, ctx->lc_hmid, ctx->xg, R, W.bd, us_done);
       ctx->lc_active = false;
       CTX_RC(rc);
       break;
@@ -1001,19 +979,19 @@ int forward(CtxT<AT>* ctx, bool stash) {
       CTX_RC(nrc);
     }
     if (!u_gu && !(whatif() & 1)) CTX_RC(norm_fwd<AT>(ctx, A.hmid, W.mlp_norm, W.mlp_norm_b, A.xn2, A.rstd2, T));
-    CTX_RC(linear_fwd<AT>(ctx, A.xn2, d, W.Wgu, ctx->Fgu, W.g_gu, A.us_gu, nullptr, A.gu, T, W.bgu, ctx->fuse_sw_fwd ? A.act : nullptr, u_gu));
+    CTX_RC(linear_fwd<AT>(ctx, A.xn2, d, W.Wgu, ctx->Fgu, W.g_gu, A.us_gu, nullptr, A.gu, T, W.bgu, u_gu));
     bool us_done = false;
     if (ctx->gpt2) CTX_RC(gelu_fwd<AT>(st, A.gu, A.act, (long)T * ctx->F));
-    else if (!ctx->fuse_sw_fwd) {
+    else {
       const int slot = prof_begin(ctx, st, ctx->prof_hbm);
       SwiRank sr;
       if (swr_setup<AT>(ctx, W.g_d, false, T, A.us_d, sr)) {   // act AND the down projection's us = s act . Ag^T in one pass over gate | up
         if constexpr (sizeof(AT) == 2) CTX_RC(swiglu_rank_fwd(st, A.gu, A.act, T, ctx->F, sr));
         us_done = true;
-      } else if (!(whatif() & 4)) CTX_RC(swiglu_fwd<AT>(st, A.gu, A.act, T, ctx->F, ctx->gu_il));
+      } else if (!(whatif() & 4)) CTX_RC(swiglu_fwd<AT>(st, A.gu, A.act, T, ctx->F));
       prof_end(ctx, st, slot, PROF_SWIGLU, 1, 3.0 * T * ctx->F * sizeof(AT));   // read gate, up; write act
     }
-    CTX_RC(linear_fwd<AT>(ctx, A.act, ctx->F, W.Wd, d, W.g_d, A.us_d, A.hmid, x_out, T, W.bd, nullptr, us_done));
+    CTX_RC(linear_fwd<AT>(ctx, A.act, ctx->F, W.Wd, d, W.g_d, A.us_d, A.hmid, x_out, T, W.bd, us_done));
   }
   return TST_OK;
 }
@@ -1029,7 +1007,6 @@ template <typename AT>
 int head_forward(CtxT<AT>* ctx, bool stash) {
   const int R = ctx->cur_R, d = ctx->d;
   CTX_RC(opt_join(ctx));   // the head (last in the optimizer's order): from here on the stream is behind the whole step
-  ctx->fwd_small_tiles = false;
   if (R <= 0) return TST_OK;
   hipStream_t st = ctx->stream;
   if (!ctx->lc_used) CTX_RC(gather_rows<AT>(st, final_hidden(ctx, stash), ctx->d_lab_idx, ctx->xg, R, d, 0));   // (compacted last layer: forward wrote xg itself)
@@ -1073,20 +1050,12 @@ int regions_join(CtxT<AT>* ctx) {
 
 // the collected adapter-gradient contractions of one layer, as one grouped launch (bf16 path only: tn_pending stays empty otherwise)
 template <typename AT>
-int flush_tn(CtxT<AT>* ctx, bool on_side) {
+int flush_tn(CtxT<AT>* ctx) {
   if (ctx->tn_pending.empty() && ctx->tns_pending.empty()) return TST_OK;
   if (whatif() & 16) { ctx->tn_pending.clear(); ctx->tns_pending.clear(); ctx->tn_pending_flop = 0; return TST_OK; }
   int rc = TST_OK;
   if constexpr (sizeof(AT) == 2) {
     hipStream_t st = ctx->stream;
-    if (on_side && ctx->side && ctx->tn_pending.empty()) {
-      // the layer's adapter gradients beside the LAST dX contraction of the layer (q|k|v): every operand is complete here (dy of all four groups, du4, us, x),
-      // nothing on the dX chain reads the result; joined before the norm backward overwrites dX (backward())
-      CTX_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));
-      CTX_HIP(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-      st = ctx->side;
-      ctx->tns_side_open = true;
-    }
     const int slot = prof_begin(ctx, st, ctx->prof);
     for (size_t i = 0; i < ctx->tns_pending.size() && rc == TST_OK; i += TST_MAX_GROUPED) {
       const size_t n = ctx->tns_pending.size() - i < TST_MAX_GROUPED ? ctx->tns_pending.size() - i : TST_MAX_GROUPED;
@@ -1190,22 +1159,20 @@ int backward(CtxT<AT>* ctx, int num_items) {
       // the compacted last layer (forward): dxg IS the gradient of its output rows; MLP and o projection backward on those R rows, then the rows
       // go back to their token positions in front of the attention backward (zeros elsewhere: no other row of this layer's output is read)
       ctx->lc_active = true;
-      int rc = linear_bwd<AT>(ctx, ctx->dxg, d, ctx->lc_act, ctx->F, W.Wd, W.WdT, W.g_d, ctx->lc_us_d, ctx->lc_dact, R, nullptr, 0, ctx->fuse_sw_bwd ? ctx->lc_gu : nullptr,
-                              ctx->fuse_sw_bwd ? ctx->lc_dgu : nullptr);
+      int rc = linear_bwd<AT>(ctx, ctx->dxg, d, ctx->lc_act, ctx->F, W.Wd, W.WdT, W.g_d, ctx->lc_us_d, ctx->lc_dact, R, nullptr, 0);
       bool du_done = false;
       if (rc == TST_OK) {
         SwiRank sr;
         if (ctx->gpt2) rc = gelu_bwd<AT>(st, ctx->lc_dact, ctx->lc_gu, ctx->lc_dgu, (long)R * ctx->F);
-        else if (ctx->fuse_sw_bwd) {
-        } else if (swr_setup<AT>(ctx, W.g_gu, true, R, du_target(ctx, W.g_gu, 1), sr)) {
+        else if (swr_setup<AT>(ctx, W.g_gu, true, R, du_target(ctx, W.g_gu, 1), sr)) {
           if constexpr (sizeof(AT) == 2) rc = swiglu_rank_bwd(st, ctx->lc_dact, ctx->lc_gu, ctx->lc_dgu, R, ctx->F, sr);
           du_done = true;
-        } else rc = swiglu_bwd<AT>(st, ctx->lc_dact, ctx->lc_gu, ctx->lc_dgu, R, ctx->F, ctx->gu_il);
+        } else rc = swiglu_bwd<AT>(st, ctx->lc_dact, ctx->lc_gu, ctx->lc_dgu, R, ctx->F);
       }
-      if (rc == TST_OK) rc = linear_bwd<AT>(ctx, ctx->lc_dgu, ctx->Fgu, ctx->lc_xn2, d, W.Wgu, W.WguT, W.g_gu, ctx->lc_us_gu, ctx->lc_dxn, R, nullptr, 1, nullptr, nullptr, true, du_done);
+      if (rc == TST_OK) rc = linear_bwd<AT>(ctx, ctx->lc_dgu, ctx->Fgu, ctx->lc_xn2, d, W.Wgu, W.WguT, W.g_gu, ctx->lc_us_gu, ctx->lc_dxn, R, nullptr, 1, true, du_done);
       if (rc == TST_OK) rc = norm_bwd<AT>(ctx, ctx->lc_dxn, ctx->lc_hmid, ctx->lc_rstd2, W.mlp_norm, ctx->dxg, ctx->lc_dH, R);
       if (rc == TST_OK) rc = linear_bwd<AT>(ctx, ctx->lc_dH, d, ctx->lc_attn, ctx->dattn, W.Wo, W.WoT, W.g_o, ctx->lc_us_o, ctx->lc_dattn, R, nullptr, 2);
-      if (rc == TST_OK) rc = flush_tn(ctx, false);   // these three groups contract over the compact rows: their own launch, with the rows' slot boundaries
+      if (rc == TST_OK) rc = flush_tn(ctx);   // these three groups contract over the compact rows: their own launch, with the rows' slot boundaries
       ctx->lc_active = false;
       CTX_RC(rc);
       CTX_HIP(hipMemsetAsync(ctx->dattn_b, 0, (size_t)T * ctx->dattn * sizeof(AT), st));
@@ -1215,22 +1182,21 @@ int backward(CtxT<AT>* ctx, int num_items) {
     } else {
     // MLP block: x_out = hmid + down(act)
     if (full && W.bd) CTX_RC(colsum<AT>(st, ctx->dX, d, gof(W.bd), T, d, ctx->colred_ws));
-    CTX_RC(linear_bwd<AT>(ctx, ctx->dX, d, W.act, ctx->F, W.Wd, W.WdT, W.g_d, W.us_d, ctx->dact, T, gof(W.Wd), 0, ctx->fuse_sw_bwd ? W.gu : nullptr,
-                          ctx->fuse_sw_bwd ? ctx->dgu : nullptr));
+    CTX_RC(linear_bwd<AT>(ctx, ctx->dX, d, W.act, ctx->F, W.Wd, W.WdT, W.g_d, W.us_d, ctx->dact, T, gof(W.Wd), 0));
     bool du_done = false;
     if (ctx->gpt2) CTX_RC(gelu_bwd<AT>(st, ctx->dact, W.gu, ctx->dgu, (long)T * ctx->F));
-    else if (!ctx->fuse_sw_bwd) {
+    else {
       const int slot = prof_begin(ctx, st, ctx->prof_hbm);
       SwiRank sr;
       if (swr_setup<AT>(ctx, W.g_gu, true, T, du_target(ctx, W.g_gu, 1), sr)) {   // dgu AND the gate|up projection's du = dgu . Bg in one pass
         if constexpr (sizeof(AT) == 2) CTX_RC(swiglu_rank_bwd(st, ctx->dact, W.gu, ctx->dgu, T, ctx->F, sr));
         du_done = true;
-      } else if (!(whatif() & 4)) CTX_RC(swiglu_bwd<AT>(st, ctx->dact, W.gu, ctx->dgu, T, ctx->F, ctx->gu_il));
+      } else if (!(whatif() & 4)) CTX_RC(swiglu_bwd<AT>(st, ctx->dact, W.gu, ctx->dgu, T, ctx->F));
       prof_end(ctx, st, slot, PROF_SWIGLU, 1, 5.0 * T * ctx->F * sizeof(AT));   // read dact, gate, up; write dgate, dup
     }
     if (full && W.bgu) CTX_RC(colsum<AT>(st, ctx->dgu, ctx->Fgu, gof(W.bgu), T, ctx->Fgu, ctx->colred_ws));
     CTX_RC(ndw_wait(ctx, 1));   // (the previous layer's attention-norm reduction on the side stream reads dxn, which the contraction below overwrites)
-    CTX_RC(linear_bwd<AT>(ctx, ctx->dgu, ctx->Fgu, W.xn2, d, W.Wgu, W.WguT, W.g_gu, W.us_gu, ctx->dxn, T, gof(W.Wgu), 1, nullptr, nullptr, true, du_done));
+    CTX_RC(linear_bwd<AT>(ctx, ctx->dgu, ctx->Fgu, W.xn2, d, W.Wgu, W.WguT, W.g_gu, W.us_gu, ctx->dxn, T, gof(W.Wgu), 1, true, du_done));
     {
       int frc = TST_OK;
       if (!norm_bwd_dw<AT>(ctx, ctx->dxn, W.hmid, W.rstd2, W.mlp_norm, ctx->dX, ctx->dH, gof(W.mlp_norm), T, &frc)) {
@@ -1258,19 +1224,14 @@ int backward(CtxT<AT>* ctx, int num_items) {
     const bool input_grad = full || l > 0;
     AT* dxq = ctx->dxn;
     CTX_RC(ndw_wait(ctx, 0));   // (this layer's MLP-norm reduction on the side stream reads dxn)
-    CTX_RC(linear_bwd<AT>(ctx, ctx->dqkv_b, ctx->dqkv, W.xn1, d, W.Wqkv, W.WqkvT, W.g_qkv, W.us_qkv, dxq, T, gof(W.Wqkv), 3, nullptr, nullptr, input_grad));
-    CTX_RC(flush_tn(ctx, false));
+    CTX_RC(linear_bwd<AT>(ctx, ctx->dqkv_b, ctx->dqkv, W.xn1, d, W.Wqkv, W.WqkvT, W.g_qkv, W.us_qkv, dxq, T, gof(W.Wqkv), 3, input_grad));
+    CTX_RC(flush_tn(ctx));
     // (this layer's dy buffers (dX, dgu, dH, dqkv_b) and du4 are still intact here)
     if (!full && ctx->side && gemm_big_tile_level(-1) == 3) {
       // join: the side stream still reads this layer's dy buffers (dX, dgu, dH, dqkv_b) and du4; dX is overwritten next, the
       // others and du4 by the next layer
       CTX_HIP(hipEventRecord(ctx->ev_join, ctx->side));
       CTX_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
-    }
-    if (ctx->tns_side_open) {   // (TST_TNS_SIDE) the adapter-gradient launch on the side stream reads dX, dgu, dH, dqkv_b, du4
-      CTX_HIP(hipEventRecord(ctx->ev_join, ctx->side));
-      CTX_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
-      ctx->tns_side_open = false;
     }
     if (ctx->dw_side_open) {
       // the side stream still reads this layer's dy buffers (dX, dgu, dH, dqkv_b) for the weight gradients: dX is overwritten next, the others by the next layer
@@ -1317,7 +1278,7 @@ int refresh_transposes(CtxT<AT>* ctx) {
 }
 
 template <typename AT>
-int add_group(CtxT<AT>* ctx, int layer, LoraGroupT<AT>& g, int din, int dout, const char* const* names, const int* row0, const int* row1, const bool* on, int nmod, int il = 0) {
+int add_group(CtxT<AT>* ctx, int layer, LoraGroupT<AT>& g, int din, int dout, const char* const* names, const int* row0, const int* row1, const bool* on, int nmod) {
   const int r = ctx->cfg.lora_r;
   int nseg = 0;   // enabled modules of the group; slot 0's offsets are set here, the other slots' by build_ctx once n1 is known
   LoraGroupDescT<AT> dsc;
@@ -1336,7 +1297,7 @@ int add_group(CtxT<AT>* ctx, int layer, LoraGroupT<AT>& g, int din, int dout, co
     ++nseg;
   }
   if (nseg == 0) { g.on = false; return TST_OK; }
-  dsc.din = din; dsc.dout = dout; dsc.r = r; dsc.nmod = nseg; dsc.nslot = ctx->ns; dsc.nseg = nseg * ctx->ns; dsc.il = il;
+  dsc.din = din; dsc.dout = dout; dsc.r = r; dsc.nmod = nseg; dsc.nslot = ctx->ns; dsc.nseg = nseg * ctx->ns;
   dsc.RP = roundup(dsc.nseg * r, 64);
   dsc.scale = ctx->cfg.lora_alpha / (float)r;
   dsc.Ag = palloc<AT>(ctx, (int64_t)dsc.RP * din);
@@ -1362,8 +1323,6 @@ struct WeightRefT {
   AT* ptr = nullptr;
   int64_t numel = 0;
   int conv_in = 0, conv_out = 0;  // GPT-2 Conv1D weight: the HF tensor is [in, out]; the device tensor is [out, in]
-  int il_rows = 0, il_cols = 0;   // interleaved gate / up: the tensor's rows live in blocks of il_rows rows of il_cols elements, every
-                                  // block followed by a block of the other tensor (device pitch = 2 * il_rows * il_cols elements)
 };
 
 // GPT-2 state_dict names (modeling_gpt2.py:486-497, 637-646)
@@ -1421,10 +1380,8 @@ WeightRefT<AT> find_weight(CtxT<AT>* ctx, const char* name) {
   else if (W.bqkv && s == "self_attn.q_proj.bias") { r.ptr = W.bqkv; r.numel = ctx->dq; }
   else if (W.bqkv && s == "self_attn.k_proj.bias") { r.ptr = W.bqkv + ctx->dq; r.numel = ctx->dkv; }
   else if (W.bqkv && s == "self_attn.v_proj.bias") { r.ptr = W.bqkv + ctx->dq + ctx->dkv; r.numel = ctx->dkv; }
-  else if (s == "mlp.gate_proj.weight") { r.ptr = W.Wgu; r.numel = (int64_t)ctx->F * d; r.il_rows = ctx->gu_il; r.il_cols = d; }
-  else if (s == "mlp.up_proj.weight") {
-    r.ptr = W.Wgu + (ctx->gu_il ? (int64_t)ctx->gu_il * d : (int64_t)ctx->F * d); r.numel = (int64_t)ctx->F * d; r.il_rows = ctx->gu_il; r.il_cols = d;
-  }
+  else if (s == "mlp.gate_proj.weight") { r.ptr = W.Wgu; r.numel = (int64_t)ctx->F * d; }
+  else if (s == "mlp.up_proj.weight") { r.ptr = W.Wgu + (int64_t)ctx->F * d; r.numel = (int64_t)ctx->F * d; }
   else if (s == "mlp.down_proj.weight") { r.ptr = W.Wd; r.numel = (int64_t)d * ctx->F; }
   return r;
 }
@@ -1462,20 +1419,6 @@ int build_ctx(CtxT<AT>* ctx) {
     if (!(c.rope_factor > 0.f)) return fail(ctx, TST_EINVAL, "rope_factor must be > 0");
     if (c.rope_scaling == TST_ROPE_LLAMA3 && (!(c.rope_low_freq_factor > 0.f) || !(c.rope_high_freq_factor > c.rope_low_freq_factor) || c.rope_original_max_position <= 0))
       return fail(ctx, TST_EINVAL, "llama3 rope scaling needs 0 < rope_low_freq_factor < rope_high_freq_factor and rope_original_max_position > 0");
-  }
-  {
-    // TST_FUSE_SWIGLU=1: SwiGLU forward / backward in the epilogues of the gate|up projection and of the down projection's dX (needs
-    // gate and up interleaved: one 256-column tile then holds both). Built, bit-identical to the elementwise kernels
-    // (test_fused_swiglu_epilogues_match_the_unfused_path_bit_for_bit), and OFF by default because it does not pay on this tile:
-    // the swiglu kernels stream at 6.0 TB/s (95 % of what HBM delivers) and hide partly in the other stream's tile-grid tails, while an
-    // epilogue's extra stores / dependent loads run at one workgroup per CU with nothing to cover their latency. Measured, same box,
-    // interleaved A/B rounds (profiles/r02_fused_swiglu_ab.txt): two streams 3+2 folds 108.4 unfused vs 107.6 fused; one stream x 5
-    // stacked folds 102.2 vs 102.5; one stream x 3 folds 100.6 vs 99.5 QA-pairs/s.
-    static const int il_env = [] { const char* e = getenv("TST_FUSE_SWIGLU"); return e ? atoi(e) : 0; }();
-    ctx->gu_il = (il_env != 0 && !gpt2 && !ctx->full && sizeof(AT) == 2 && (ctx->F % 128) == 0) ? 128 : 0;
-    if (ctx->parent) ctx->gu_il = ctx->parent->gu_il;   // a fork borrows the parent's weights: same layout
-    ctx->fuse_sw_fwd = ctx->gu_il && il_env != 3;
-    ctx->fuse_sw_bwd = ctx->gu_il && il_env != 2;
   }
   if constexpr (sizeof(AT) == 2) {
     // K-major members for the full fine-tune's backward (tst_ctx::kmajor). Every contraction axis they meet (d_qkv, d, F or 2F, the padded vocabulary) is a
@@ -1616,7 +1559,7 @@ int build_ctx(CtxT<AT>* ctx) {
       { const int r0[1] = {0}, r1[1] = {d}; const bool on[1] = {(t & TST_LORA_O) != 0};
         CTX_RC(add_group(ctx, l, W.g_o, ctx->dattn, d, n_o, r0, r1, on, 1)); }
       { const int r0[2] = {0, F}, r1[2] = {F, 2 * F}; const bool on[2] = {(t & TST_LORA_GATE) != 0, (t & TST_LORA_UP) != 0};
-        CTX_RC(add_group(ctx, l, W.g_gu, d, 2 * F, n_gu, r0, r1, on, 2, ctx->gu_il)); }
+        CTX_RC(add_group(ctx, l, W.g_gu, d, 2 * F, n_gu, r0, r1, on, 2)); }
       { const int r0[1] = {0}, r1[1] = {d}; const bool on[1] = {(t & TST_LORA_DOWN) != 0};
         CTX_RC(add_group(ctx, l, W.g_d, F, d, n_d, r0, r1, on, 1)); }
     }
@@ -1864,14 +1807,6 @@ int build_ctx(CtxT<AT>* ctx) {
 template <typename AT>
 int repack(CtxT<AT>* ctx) { return lora_pack<AT>(ctx->stream, ctx->descs_dev, (int)ctx->descs.size(), ctx->tp, ctx->pack_max_long); }
 
-// uniform(-bound, bound) for lora_A, zeros for lora_B (host side, splitmix64: deterministic per (seed, tensor, element))
-inline uint64_t splitmix64(uint64_t& x) {
-  uint64_t z = (x += 0x9e3779b97f4a7c15ULL);
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-  return z ^ (z >> 31);
-}
-
 
 // ---- typed halves of the C-ABI entry points (dispatched on ctx->strict below)
 template <typename AT>
@@ -1935,11 +1870,6 @@ int set_weight_impl(CtxT<AT>* ctx, const char* name, const void* host, int dtype
     }
     src = tmp.data();
   }
-  if (w.il_rows) {   // blocks of il_rows rows, every second block of the device tensor
-    const size_t blk = (size_t)w.il_rows * w.il_cols * sizeof(AT);
-    CTX_HIP(hipMemcpy2D(w.ptr, 2 * blk, src, blk, blk, (size_t)(numel / ((int64_t)w.il_rows * w.il_cols)), hipMemcpyHostToDevice));
-    return TST_OK;
-  }
   CTX_HIP(hipMemcpy(w.ptr, src, (size_t)numel * sizeof(AT), hipMemcpyHostToDevice));
   return TST_OK;
 }
@@ -1951,12 +1881,7 @@ int get_weight_impl(CtxT<AT>* ctx, const char* name, float* host_out, int64_t nu
   if (w.numel != numel) return fail(ctx, TST_EINVAL, std::string("numel mismatch for ") + name);
   std::vector<AT> tmp((size_t)numel);
   CTX_RC(ctx_sync(ctx));
-  if (w.il_rows) {
-    const size_t blk = (size_t)w.il_rows * w.il_cols * sizeof(AT);
-    CTX_HIP(hipMemcpy2D(tmp.data(), blk, w.ptr, 2 * blk, blk, (size_t)(numel / ((int64_t)w.il_rows * w.il_cols)), hipMemcpyDeviceToHost));
-  } else {
-    CTX_HIP(hipMemcpy(tmp.data(), w.ptr, (size_t)numel * sizeof(AT), hipMemcpyDeviceToHost));
-  }
+  CTX_HIP(hipMemcpy(tmp.data(), w.ptr, (size_t)numel * sizeof(AT), hipMemcpyDeviceToHost));
   auto val = [&](int64_t i) -> float {
     if (sizeof(AT) == 2) { uint16_t b; memcpy(&b, &tmp[(size_t)i], 2); return host_bf2f(b); }
     float v; memcpy(&v, &tmp[(size_t)i], sizeof(AT) < 4 ? sizeof(AT) : 4); return v;
@@ -2064,48 +1989,22 @@ int reset_trainable_impl(CtxT<AT>* ctx, uint64_t seed) {
   }
   // LoRA: the selected slot's adapters (one slot unless folds are stacked)
   const int64_t so = ctx->sel_slot * ctx->n1;
-  static const bool host_rng = env_flag("TST_RESET_HOST", false);   // (A/B switch: the serial host loop + blocking copies this path had until round 3)
-  if (!host_rng) {
-    // everything on the context's stream, nothing the host waits for: lora_B, both moments and the gradient are zeros, every lora_A is drawn on the
-    // device (same splitmix64 stream per (seed, tensor), same values as the host loop below), then the packed operands are rebuilt
-    hipStream_t st = ctx->stream;
-    CTX_HIP(hipMemsetAsync(ctx->tp + so, 0, (size_t)ctx->n1 * 4, st));
-    CTX_HIP(hipMemsetAsync(ctx->tm + so, 0, (size_t)ctx->n1 * 4, st));
-    CTX_HIP(hipMemsetAsync(ctx->tv + so, 0, (size_t)ctx->n1 * 4, st));
-    CTX_HIP(hipMemsetAsync(ctx->tg + so, 0, (size_t)ctx->n1 * 4, st));
-    for (size_t t = 0; t < ctx->tinfo.size(); ++t) {
-      const TrainableInfo& ti = ctx->tinfo[t];
-      if (!(ti.name.size() > 6 && ti.name.compare(ti.name.size() - 6, 6, "lora_A") == 0)) continue;
-      const uint64_t state0 = seed * 0x9e3779b97f4a7c15ULL + (uint64_t)t * 0xd1b54a32d192ed03ULL + 1;
-      CTX_RC(lora_a_init(st, ctx->tp + so + ti.offset, (long)(ti.rows * ti.cols), state0, 1.0f / sqrtf((float)ti.cols)));
-    }
-    ctx->opt_steps[ctx->sel_slot] = 0;
-    return repack(ctx);
-  }
-  std::vector<float> h((size_t)ctx->n1, 0.f);
+  // everything on the context's stream, nothing the host waits for: lora_B, both moments and the gradient are zeros, every lora_A is drawn on the
+  // device (one splitmix64 stream per (seed, tensor); peft: kaiming_uniform_(A, a=sqrt(5)) => U(-1/sqrt(fan_in), 1/sqrt(fan_in))), then the packed
+  // operands are rebuilt
+  hipStream_t st = ctx->stream;
+  CTX_HIP(hipMemsetAsync(ctx->tp + so, 0, (size_t)ctx->n1 * 4, st));
+  CTX_HIP(hipMemsetAsync(ctx->tm + so, 0, (size_t)ctx->n1 * 4, st));
+  CTX_HIP(hipMemsetAsync(ctx->tv + so, 0, (size_t)ctx->n1 * 4, st));
+  CTX_HIP(hipMemsetAsync(ctx->tg + so, 0, (size_t)ctx->n1 * 4, st));
   for (size_t t = 0; t < ctx->tinfo.size(); ++t) {
     const TrainableInfo& ti = ctx->tinfo[t];
-    const bool isA = ti.name.size() > 6 && ti.name.compare(ti.name.size() - 6, 6, "lora_A") == 0;
-    if (!isA) continue;
-    // peft: kaiming_uniform_(A, a=sqrt(5)) => U(-1/sqrt(fan_in), 1/sqrt(fan_in))
-    const float bound = 1.0f / sqrtf((float)ti.cols);
-    uint64_t state = seed * 0x9e3779b97f4a7c15ULL + (uint64_t)t * 0xd1b54a32d192ed03ULL + 1;
-    for (int64_t i = 0; i < ti.rows * ti.cols; ++i) {
-      const uint64_t z = splitmix64(state);
-      const float u = (float)((z >> 40) + 0.5) * (1.0f / 16777216.0f);  // (0,1)
-      h[(size_t)(ti.offset + i)] = (2.0f * u - 1.0f) * bound;
-    }
+    if (!(ti.name.size() > 6 && ti.name.compare(ti.name.size() - 6, 6, "lora_A") == 0)) continue;
+    const uint64_t state0 = seed * 0x9e3779b97f4a7c15ULL + (uint64_t)t * 0xd1b54a32d192ed03ULL + 1;
+    CTX_RC(lora_a_init(st, ctx->tp + so + ti.offset, (long)(ti.rows * ti.cols), state0, 1.0f / sqrtf((float)ti.cols)));
   }
-  CTX_RC(ctx_sync(ctx));
-  CTX_HIP(hipMemcpy(ctx->tp + so, h.data(), h.size() * 4, hipMemcpyHostToDevice));
-  CTX_HIP(hipMemset(ctx->tm + so, 0, (size_t)ctx->n1 * 4));
-  CTX_HIP(hipMemset(ctx->tv + so, 0, (size_t)ctx->n1 * 4));
-  CTX_HIP(hipMemset(ctx->tg + so, 0, (size_t)ctx->n1 * 4));
-  CTX_HIP(hipDeviceSynchronize());
   ctx->opt_steps[ctx->sel_slot] = 0;
-  CTX_RC(repack(ctx));
-  CTX_RC(ctx_sync(ctx));
-  return TST_OK;
+  return repack(ctx);
 }
 
 // slot_items: per-slot labelled-token counts of the whole accumulated / global batch (nullptr: every slot is normalised by its own count in b)

@@ -529,27 +529,6 @@ int gemm_pp_kmajor(hipStream_t st, GemmParams p, float* slab_ws, size_t slab_ws_
 int gemm_nt(hipStream_t st, GemmParams p, float* slab_ws, size_t slab_ws_bytes, int force_variant, int force_splitk, int* used) {
   if (p.M <= 0 || p.N <= 0 || (p.K + p.K2) <= 0) return TST_EINVAL;
   if (p.ta || p.tb) return TST_EINVAL;   // K-major operands: gemm_pp_kmajor
-  if (p.act_out || p.sw_dgu) {
-    // fused SwiGLU epilogues: only the unsplit 256x256 ping-pong tile has them; every other tile family runs the contraction as it
-    // is and the elementwise kernel behind it (same arithmetic on the same bf16-rounded values: bit-identical results)
-    if (p.il != 128 || p.out_f32 || p.mask_width || (p.act_out && (p.sw_dgu || (p.N & 255))) || (p.sw_dgu && (!p.sw_gu || p.R || p.bias || (p.N & 127) || !p.C)))
-      return TST_EINVAL;
-    int v0, s0;
-    gemm_plan(p.M, p.N, p.K, p.K2, &v0, &s0);
-    static const int kind = [] { const char* e = getenv("TST_BIG_KIND"); return e ? atoi(e) : 5; }();
-    const bool pp = (force_variant == 5 || (force_variant < 0 && v0 == 4 && kind == 5)) && gemm_pp_supported(p);
-    if (pp) {
-      if (used) { used[0] = 5; used[1] = 1; }
-      p.splitk = 1; p.slab = slab_ws; p.slab_cap = slab_ws_bytes;
-      return gemm_pp(st, p);
-    }
-    GemmParams q = p;
-    q.act_out = nullptr; q.sw_gu = nullptr; q.sw_dgu = nullptr;
-    const int rc = gemm_nt(st, q, slab_ws, slab_ws_bytes, force_variant, force_splitk, used);
-    if (rc != TST_OK) return rc;
-    if (p.act_out) return swiglu_fwd<bf16_t>(st, (const bf16_t*)p.C, p.act_out, p.M, p.N >> 1, p.il);
-    return swiglu_bwd<bf16_t>(st, (const bf16_t*)p.C, p.sw_gu, p.sw_dgu, p.M, p.N, p.il);
-  }
   if ((p.K & 63) || (p.K2 & 63) || (p.N & 7)) return TST_EINVAL;
   if ((p.lda & 7) || (p.ldb & 7) || (p.K2 && ((p.lda2 & 7) || (p.ldb2 & 7)))) return TST_EINVAL;
   if (p.out_f32 ? (p.ldc & 3) : (p.ldc & 7)) return TST_EINVAL;

@@ -133,8 +133,7 @@ __device__ __forceinline__ void tr_wait_b(BSub& b, BRaw& r) {
     for (int ni = 0; ni < 2; ++ni) b.f[kk][ni] = tr_join(r.h[kk][ni][0], r.h[kk][ni][1]);
 }
 template <int MH, int NH>
-__device__ __forceinline__ void mma16(f32x4 (&acc)[8][4], const ASub& a, const BSub& b, bool on = true) {
-  if (!on) return;   // (wave-uniform) tail-skip build: this wave's 64 rows of the phase lie beyond M
+__device__ __forceinline__ void mma16(f32x4 (&acc)[8][4], const ASub& a, const BSub& b) {
   __builtin_amdgcn_s_setprio(1);
   // (a boustrophedon order over (mi, ni), consecutive MFMAs sharing an operand fragment, changes neither the rate nor the power: 1430 / 1430 TFLOP/s, round 5)
 #pragma unroll
@@ -181,15 +180,9 @@ __device__ __forceinline__ void pp_tile_of(const GemmParams& p, int vbid, int& t
 
 // STAMP: diagnostic build (never on the product path): lane 0 of waves 0 and 4 of workgroup 0 stores s_memtime after every
 // barrier of the main loop into stamps[group][i] (a buffer nothing else reads), to see how long each phase really takes.
-// EPI: 0 = plain epilogue; 1 = + fused SwiGLU forward (p.act_out); 2 = fused SwiGLU backward (p.sw_dgu) -- separate instantiations, so
-// the plain kernel's register allocation (256 VGPRs, no spill) is untouched by the fused epilogues' extra live values
-// TS ("tail skip"): a build whose waves skip the MFMAs of a 64-row block that lies entirely beyond M. The last tile row of a token count
-// that is not a multiple of 256 (M = 2370 of two stacked folds: 66 of 256 rows) otherwise costs a full tile time for its padding: with
-// the skip the SIMDs' MFMA pipe time of such a tile falls with its valid 64-row blocks (barriers and DMA unchanged). Launched only when the
-// last tile row has a skippable block (gemm_pp()), so full-tile launches keep the plain build.
 // TA / TB: the K-major members (transposed reads above): A given as [K][M] and / or B as [K][N]; no second K segment, plain epilogue. Rows of a K-major operand beyond
 // p.kvalid (TN: the token count, not a multiple of 64) are OUT OF RANGE of the buffer descriptor the k-tile is staged through and arrive as zeros.
-template <bool STAMP, int EPI = 0, bool TS = false, bool TA = false, bool TB = false>
+template <bool STAMP, bool TA = false, bool TB = false>
 __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p, unsigned long long* stamps) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the body uses buffer-resource types that only exist in the device pass
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -250,9 +243,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p, unsigned 
   for (int i = 0; i < 8; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // tail skip: does this wave's m-half MH (rows m0 + 128 wr + 64 MH ...) hold any row < M?
-  const bool mma_on0 = !TS || __builtin_amdgcn_readfirstlane(m0 + wr * 128 < p.M ? 1 : 0) != 0;
-  const bool mma_on1 = !TS || __builtin_amdgcn_readfirstlane(m0 + wr * 128 + 64 < p.M ? 1 : 0) != 0;
 
   // Staging through buffer_load ... lds: the per-thread part of every address (clamped row x leading dimension + swizzled
   // chunk) is loop-invariant and lives in 8 VGPRs; the k position travels in the scalar offset and the LDS destination in
@@ -358,7 +348,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p, unsigned 
     PP_BARRIER();
     stamp();
     if constexpr (TA) tr_wait_a(A, Ar);
-    mma16<0, 0>(acc, A, Bn0[PAR], mma_on0);
+    mma16<0, 0>(acc, A, Bn0[PAR]);
     PP_BARRIER();
     stamp();
     // ---- phase 2: (m0, n1)
@@ -369,7 +359,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p, unsigned 
     else PP_RETIRE_READS();
     PP_BARRIER();
     stamp();
-    mma16<0, 1>(acc, A, Bn1, mma_on0);
+    mma16<0, 1>(acc, A, Bn1);
     PP_BARRIER();
     stamp();
     // ---- phase 3: (m1, n1)
@@ -385,7 +375,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p, unsigned 
     PP_BARRIER();
     stamp();
     if constexpr (TA) tr_wait_a(A, Ar);
-    mma16<1, 1>(acc, A, Bn1, mma_on1);
+    mma16<1, 1>(acc, A, Bn1);
     PP_BARRIER();
     stamp();
     // ---- phase 4: (m1, n0); B n0 of the next tile is read here (its half-tile was retired in phase 3)
@@ -403,7 +393,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p, unsigned 
     PP_BARRIER();
     stamp();
     if constexpr (TB) { if (more1) tr_wait_b(Bn0[PAR ^ 1], Bn0r[PAR ^ 1]); }   // (read here, used from the next k-tile's phase 1 on: retired and joined before anything can copy it)
-    mma16<1, 0>(acc, A, Bn0[PAR], mma_on1);
+    mma16<1, 0>(acc, A, Bn0[PAR]);
     PP_BARRIER();
     stamp();
   };
@@ -422,49 +412,6 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p, unsigned 
     }
   };
 
-  if constexpr (EPI == 2) {
-    // ---- fused SwiGLU backward (dX of the down projection; no split, no tail, no residual / bias: gemm_nt checks): the tile is d(act) and is
-    // consumed here, never stored. BOTH wave groups round their accumulators to bf16 (the precision swiglu_bwd_kernel reads d(act) back at)
-    // and drop them into ONE 256 x 256 bf16 image (128 KB: the whole tile fits once it is bf16), so no wave carries 128 accumulator
-    // registers through the SwiGLU arithmetic -- round 2's form of this epilogue went through the two fp32 slabs and spilled 24 VGPRs there.
-    __syncthreads();
-    char* Cb = smem;   // row r: 512 bytes, 16-byte chunk c at ((c ^ (r & 31)) << 4)
-#pragma unroll
-    for (int mi = 0; mi < 8; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) {
-        const int row = wr * 128 + mi * 16 + fr;
-        const int col = wc * 64 + ni * 16 + fg * 4;
-        f32x4 v = acc[mi][ni];
-        v *= p.alpha;
-        uint2 o;
-        o.x = pack2bf(v[0], v[1]); o.y = pack2bf(v[2], v[3]);
-        *(uint2*)(Cb + row * 512 + (((col >> 3) ^ (row & 31)) << 4) + ((col & 4) << 1)) = o;
-      }
-    __syncthreads();
-    const int c8 = tid & 31, r0 = tid >> 5;
-#pragma unroll 2
-    for (int pass = 0; pass < 16; ++pass) {
-      const int row = pass * 16 + r0;
-      const int gm = m0 + row, gn = n0 + c8 * 8;
-      if (gm < p.M && gn < p.N) {
-        float da[8], g[8], u[8], dg[8], du[8];
-        ld8((const bf16_t*)(Cb + row * 512 + ((c8 ^ (row & 31)) << 4)), da);
-        const long o = (long)gm * (2L * p.N) + (long)(gn / p.il) * 2 * p.il + gn % p.il;
-        ld8(p.sw_gu + o, g);
-        ld8(p.sw_gu + o + p.il, u);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {   // the arithmetic of swiglu_bwd_kernel on the bf16-rounded d(act)
-          const float sg = sigmoid_of<bf16_t>(g[j]);
-          dg[j] = da[j] * u[j] * sg * (1.0f + g[j] * (1.0f - sg));
-          du[j] = da[j] * g[j] * sg;
-        }
-        st8(p.sw_dgu + o, dg);
-        st8(p.sw_dgu + o + p.il, du);
-      }
-    }
-    return;
-  }
   // ---- epilogue (as gemm_big.hip): two 128-row slabs through LDS (XOR-swizzled 16-B chunks), whole-row stores
   float* Cs = (float*)smem;
   float ss = 0.f;   // p.sumsq: sum of squares of the fp32 values this thread stores (weight gradients feed the global norm)
@@ -500,8 +447,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p, unsigned 
         const int gm = m0 + h * 128 + row, gn = n0 + c4 * 4;
         if (gm < p.M && gn < p.N) {
           const f32x4 v = *(const f32x4*)(Cs + row * BN + ((c4 ^ (row & 7)) << 2));
-          if (TA && TB && p.nt_out) __builtin_nontemporal_store(v, (f32x4*)(dst + (long)gm * ldo + gn));
-          else *(f32x4*)(dst + (long)gm * ldo + gn) = v;
+          *(f32x4*)(dst + (long)gm * ldo + gn) = v;
           ss += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
         }
       }
@@ -528,32 +474,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p, unsigned 
             v1[0] += __uint_as_float(rr.z << 16); v1[1] += __uint_as_float(rr.z & 0xffff0000u);
             v1[2] += __uint_as_float(rr.w << 16); v1[3] += __uint_as_float(rr.w & 0xffff0000u);
           }
-          {
-            uint4 o;
-            o.x = pack2bf(v0[0], v0[1]); o.y = pack2bf(v0[2], v0[3]);
-            o.z = pack2bf(v1[0], v1[1]); o.w = pack2bf(v1[2], v1[3]);
-            *(uint4*)(dst + (long)gm * p.ldc + gn) = o;
-            if (EPI == 1 && c8 < 16) {
-              // fused SwiGLU forward (gate|up projection, interleaved in blocks of 128 = half a tile): this thread's 8 columns are
-              // gate values, the matching up values sit 128 columns to the right in the same LDS row
-              f32x4 u0 = *(const f32x4*)(Cs + row * BN + (((2 * (c8 + 16)) ^ (row & 7)) << 2));
-              f32x4 u1 = *(const f32x4*)(Cs + row * BN + (((2 * (c8 + 16) + 1) ^ (row & 7)) << 2));
-              if (p.bias) {
-                float b[8];
-                ld8(p.bias + gn + 128, b);
-                u0[0] += b[0]; u0[1] += b[1]; u0[2] += b[2]; u0[3] += b[3]; u1[0] += b[4]; u1[1] += b[5]; u1[2] += b[6]; u1[3] += b[7];
-              }
-              const float gg[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-              const float uu[8] = {u0[0], u0[1], u0[2], u0[3], u1[0], u1[1], u1[2], u1[3]};
-              float a[8];
-#pragma unroll
-              for (int j = 0; j < 8; ++j) {   // on the bf16-rounded gate / up values, exactly as swiglu_fwd_kernel reads them back
-                const float gj = rnd_as<bf16_t>(gg[j]), uj = rnd_as<bf16_t>(uu[j]);
-                a[j] = swiglu_of<bf16_t>(gj, uj);
-              }
-              st8(p.act_out + (long)gm * (p.N >> 1) + (n0 >> 1) + c8 * 8, a);
-            }
-          }
+          uint4 o;
+          o.x = pack2bf(v0[0], v0[1]); o.y = pack2bf(v0[2], v0[3]);
+          o.z = pack2bf(v1[0], v1[1]); o.w = pack2bf(v1[2], v1[3]);
+          *(uint4*)(dst + (long)gm * p.ldc + gn) = o;
         }
       }
     }
@@ -631,11 +555,11 @@ bool gemm_pp_supported(const GemmParams& p) {
   if (p.ta || p.tb) return gemm_pp_kmajor_supported(p);
   return fits(p.M, p.lda, p.K) && fits(p.N, p.ldb, p.K) && (!p.K2 || (fits(p.M, p.lda2, p.K2) && fits(p.N, p.ldb2, p.K2)));
 }
-// K-major members: a K-major operand is [K rows][cols]; no second K segment, no fused epilogue, no slot mask; TN (ta && tb) or NN (tb only)
+// K-major members: a K-major operand is [K rows][cols]; no second K segment, no slot mask; TN (ta && tb) or NN (tb only)
 bool gemm_pp_kmajor_supported(const GemmParams& p) {
   const long lim = 0x7fffffffL;
   auto fits = [&](long rows, long ld, long k) { return (rows * ld + k) * 2 < lim; };
-  if (!p.tb || p.K2 || p.act_out || p.sw_dgu || p.mask_width || p.k2_w || (p.K & 63) || p.K <= 0 || p.N < 8 || (p.N & 7) || (p.ta && (p.M < 8 || (p.M & 7))) || (p.lda & 7) || (p.ldb & 7)) return false;
+  if (!p.tb || p.K2 || p.mask_width || p.k2_w || (p.K & 63) || p.K <= 0 || p.N < 8 || (p.N & 7) || (p.ta && (p.M < 8 || (p.M & 7))) || (p.lda & 7) || (p.ldb & 7)) return false;
   if (p.kvalid < 0 || p.kvalid > p.K || (p.kvalid > 0 && !p.ta) || p.lda >= (1L << 23) || p.ldb >= (1L << 23)) return false;   // a short last k-tile exists in the TN form only (both operands K-major)
   return (p.ta ? fits(p.K, p.lda, p.M) : fits(p.M, p.lda, p.K)) && fits(p.K, p.ldb, p.N);
 }
@@ -644,10 +568,9 @@ int gemm_pp(hipStream_t st, GemmParams p) {
   constexpr int LDS = 2 * BUF;
   if (!gemm_pp_supported(p)) return (p.ta || p.tb) ? TST_EINVAL : gemm_big(st, p);
   static TstLdsAttr attr_set;   // per device: tst_create accepts any device index
-  if (tst_set_max_lds(attr_set, {{(const void*)gemm_pp_kernel<false, 0>, LDS}, {(const void*)gemm_pp_kernel<false, 1>, LDS}, {(const void*)gemm_pp_kernel<false, 2>, LDS},
-                                 {(const void*)gemm_pp_kernel<true, 0>, LDS}, {(const void*)gemm_pp_kernel<false, 0, true>, LDS},
-                                 {(const void*)gemm_pp_kernel<false, 0, false, true, true>, LDS}, {(const void*)gemm_pp_kernel<false, 0, false, false, true>, LDS},
-                                 {(const void*)gemm_pp_kernel<true, 0, false, true, true>, LDS}, {(const void*)gemm_pp_kernel<true, 0, false, false, true>, LDS}}) != TST_OK)
+  if (tst_set_max_lds(attr_set, {{(const void*)gemm_pp_kernel<false>, LDS}, {(const void*)gemm_pp_kernel<true>, LDS},
+                                 {(const void*)gemm_pp_kernel<false, true, true>, LDS}, {(const void*)gemm_pp_kernel<false, false, true>, LDS},
+                                 {(const void*)gemm_pp_kernel<true, true, true>, LDS}, {(const void*)gemm_pp_kernel<true, false, true>, LDS}}) != TST_OK)
     return TST_EHIP;
   p.mtiles = tst_ceil_div(p.M, BM);
   p.ntiles = tst_ceil_div(p.N, BN);
@@ -658,8 +581,7 @@ int gemm_pp(hipStream_t st, GemmParams p) {
     const int groups = tst_ceil_div(p.mtiles, want);
     p.gm = env_gm == 0 ? p.mtiles : tst_ceil_div(p.mtiles, groups);
   }
-  if (p.splitk < 1 || !p.slab || p.act_out || p.sw_dgu) p.splitk = 1;   // the caller sets splitk > 1 together with a slab of splitk*M*N floats and runs the reduce;
-                                                                     // the fused SwiGLU epilogues exist in the unsplit tile only
+  if (p.splitk < 1 || !p.slab) p.splitk = 1;   // the caller sets splitk > 1 together with a slab of splitk*M*N floats and runs the reduce
   if (p.splitk > (p.K + p.K2) / 64) p.splitk = (p.K + p.K2) / 64;
   int grid = p.mtiles * p.ntiles * p.splitk;
   p.tail_s = 1; p.tail_full = 0; p.tail_n = 0;
@@ -671,7 +593,7 @@ int gemm_pp(hipStream_t st, GemmParams p) {
     static const int tail_env = [] { const char* e = getenv("TST_PP_TAIL"); return e ? atoi(e) : -1; }();
     const bool tail_on = tail_env >= 0 ? tail_env != 0 : (gemm_big_tile_level(-1) == 3 && !p.no_tail);
     const int nwg = p.mtiles * p.ntiles, full = nwg / 256 * 256, tail = nwg - full, nt_all = (p.K + p.K2) / 64;
-    if (tail_on && p.splitk == 1 && p.slab && full > 0 && tail > 0 && tail <= 128 && !g_pp_stamps && !p.act_out && !p.sw_dgu) {
+    if (tail_on && p.splitk == 1 && p.slab && full > 0 && tail > 0 && tail <= 128 && !g_pp_stamps) {
       int sp = 256 / tail;
       if (sp > 8) sp = 8;
       while (sp > 1 && nt_all / sp < 8) --sp;   // at least 8 k-tiles per slice: the pipeline prologue stays small
@@ -681,22 +603,12 @@ int gemm_pp(hipStream_t st, GemmParams p) {
       }
     }
   }
-  if (p.ta && p.tb && g_pp_stamps) hipLaunchKernelGGL((gemm_pp_kernel<true, 0, false, true, true>), dim3(grid), dim3(NT), LDS, st, p, g_pp_stamps);
-  else if (p.tb && g_pp_stamps) hipLaunchKernelGGL((gemm_pp_kernel<true, 0, false, false, true>), dim3(grid), dim3(NT), LDS, st, p, g_pp_stamps);
-  else if (p.ta && p.tb) hipLaunchKernelGGL((gemm_pp_kernel<false, 0, false, true, true>), dim3(grid), dim3(NT), LDS, st, p, (unsigned long long*)nullptr);
-  else if (p.tb) hipLaunchKernelGGL((gemm_pp_kernel<false, 0, false, false, true>), dim3(grid), dim3(NT), LDS, st, p, (unsigned long long*)nullptr);
-  else if (p.sw_dgu) hipLaunchKernelGGL((gemm_pp_kernel<false, 2>), dim3(grid), dim3(NT), LDS, st, p, (unsigned long long*)nullptr);
-  else if (p.act_out) hipLaunchKernelGGL((gemm_pp_kernel<false, 1>), dim3(grid), dim3(NT), LDS, st, p, (unsigned long long*)nullptr);
-  else if (g_pp_stamps) hipLaunchKernelGGL((gemm_pp_kernel<true, 0>), dim3(grid), dim3(NT), LDS, st, p, g_pp_stamps);
-  else {
-    // tail skip (TST_PP_TAILSKIP=1 turns it on: A/B switch). OFF by default: measured -1.0 % on the two-stream bench (107.0 vs 105.9 QA-pairs/s,
-    // three interleaved rounds, profiles/r03_ab_pp_tail_skip.txt): the wave-uniform branches around the four MFMA clusters of a k-tile cost the
-    // FULL tiles (13 of 14 tile rows) more -- the launch average rises from 414 to 420 us -- than the padded last row gains.
-    static const bool ts_env = [] { const char* e = getenv("TST_PP_TAILSKIP"); return e && atoi(e) != 0; }();
-    const int vrows = p.M % BM;
-    if (ts_env && vrows != 0 && vrows <= 192) hipLaunchKernelGGL((gemm_pp_kernel<false, 0, true>), dim3(grid), dim3(NT), LDS, st, p, (unsigned long long*)nullptr);
-    else hipLaunchKernelGGL((gemm_pp_kernel<false, 0>), dim3(grid), dim3(NT), LDS, st, p, (unsigned long long*)nullptr);
-  }
+  if (p.ta && p.tb && g_pp_stamps) hipLaunchKernelGGL((gemm_pp_kernel<true, true, true>), dim3(grid), dim3(NT), LDS, st, p, g_pp_stamps);
+  else if (p.tb && g_pp_stamps) hipLaunchKernelGGL((gemm_pp_kernel<true, false, true>), dim3(grid), dim3(NT), LDS, st, p, g_pp_stamps);
+  else if (p.ta && p.tb) hipLaunchKernelGGL((gemm_pp_kernel<false, true, true>), dim3(grid), dim3(NT), LDS, st, p, (unsigned long long*)nullptr);
+  else if (p.tb) hipLaunchKernelGGL((gemm_pp_kernel<false, false, true>), dim3(grid), dim3(NT), LDS, st, p, (unsigned long long*)nullptr);
+  else if (g_pp_stamps) hipLaunchKernelGGL((gemm_pp_kernel<true>), dim3(grid), dim3(NT), LDS, st, p, g_pp_stamps);
+  else hipLaunchKernelGGL((gemm_pp_kernel<false>), dim3(grid), dim3(NT), LDS, st, p, (unsigned long long*)nullptr);
   if (p.tail_s > 1) hipLaunchKernelGGL(pp_tail_reduce_kernel, dim3(16, p.tail_n), dim3(256), 0, st, p);
   return hipGetLastError() == hipSuccess ? TST_OK : TST_EHIP;
 }

@@ -298,8 +298,8 @@ __global__ __launch_bounds__(RL_NW * 64) void gemm_rank_lds_kernel(GemmParams p)
 }  // namespace
 
 bool gemm_rank_supported(const GemmParams& p) {
-  return p.M > 0 && p.N >= 16 && p.N <= 512 && (p.N & 15) == 0 && p.K >= 64 && (p.K & 63) == 0 && p.K2 == 0 && !p.out_f32 && !p.R && !p.bias && !p.act_out &&
-         !p.sw_dgu && (p.lda & 7) == 0 && (p.ldb & 7) == 0 && (p.ldc & 3) == 0 && (!p.mask_width || ((p.mask_width & 3) == 0 && p.mask_nslot >= 1 && p.mask_nslot <= TST_MAX_STACK));
+  return p.M > 0 && p.N >= 16 && p.N <= 512 && (p.N & 15) == 0 && p.K >= 64 && (p.K & 63) == 0 && p.K2 == 0 && !p.out_f32 && !p.R && !p.bias &&
+         (p.lda & 7) == 0 && (p.ldb & 7) == 0 && (p.ldc & 3) == 0 && (!p.mask_width || ((p.mask_width & 3) == 0 && p.mask_nslot >= 1 && p.mask_nslot <= TST_MAX_STACK));
 }
 
 // rows per workgroup: 16 gives 2x the workgroups (M = 3555: 223 for 256 CUs) at 2x the B re-reads from L2; TST_RANK_BM overrides (A/B switch)

@@ -23,7 +23,7 @@ struct GemmParamsT {
   int kvalid;                            // TN forms only: real rows of the contraction axis (K = kvalid rounded up to 64)
   int ta, tb;                            // 256x256 ping-pong tile only (gemm_pp_kmajor): the operand is stored K-major -- ta: A is [K][M] (lda), tb: B is [K][N] (ldb).
                                          // ta = tb = 1 is the TN form (dW = dy^T . x straight from the row-major activations; rows >= kvalid read as zeros),
-                                         // ta = 0, tb = 1 the NN form (dX = dY . W from the one stored W[K = d_out][N = d_in]); no second K segment, no fused epilogues
+                                         // ta = 0, tb = 1 the NN form (dX = dY . W from the one stored W[K = d_out][N = d_in]); no second K segment
   int out_f32;
   int splitk;                            // set by gemm_nt
   float alpha;
@@ -32,8 +32,6 @@ struct GemmParamsT {
   int tail_s, tail_full, tail_n;         // gemm_pp tail split (set by gemm_pp): K slices per tail tile, first tail block, tail tiles
   int no_splitk;                         // caller's veto of the tile policy's split-K on the 256x256 tile (same reason as no_tail)
   int no_tail;                           // caller's veto of the tail split: the stream does not have the GPU to itself (full fine-tune: weight gradients / AdamW run beside it)
-  int nt_out;                            // TN member, fp32 output: non-temporal stores (a weight gradient is written once and read by the optimizer a backward later:
-                                         // its 4 B/param should not evict the W / activation lines the contractions beside it re-read)
   size_t slab_cap;                       // bytes behind slab (set by gemm_nt)
   float* sumsq;                          // optional, fp32 output on the 256x256 ping-pong tile without split-K: per-workgroup sums of squares of the
                                          // stored values, slots [0, mtiles*ntiles) (+ 16 per tail tile behind the full waves); unused slots are not written
@@ -42,15 +40,6 @@ struct GemmParamsT {
   int k2_w;                              // stacked folds, second K segment: row t of A2 is zero outside the column block [s*k2_w, (s+1)*k2_w) of its slot s (slots from
                                          // mask_nslot / mask_ends, which may be set with mask_width == 0). The 256x256 ping-pong tile then runs only the K2 k-tiles that
                                          // overlap the blocks of its rows' slots (the others add exact zeros); every other tile family ignores it. 0 = all of K2
-  // fused SwiGLU epilogues (bf16 path, 256x256 ping-pong tile; gemm_nt() runs the elementwise kernel behind any other tile family).
-  // Gate and up live INTERLEAVED in blocks of `il` (= 128) columns: block b of the [M, 2F] tensor holds gate columns
-  // [b*il, (b+1)*il) in its first il columns and the matching up columns in the next il, so one 256-column tile has both.
-  //   forward  (the gate|up projection, N = 2F): act_out[M, F] (ld F) = silu(gate) * up, written beside C
-  //   backward (the dX of the down projection, N = F): C = d(act) is NOT stored; sw_dgu[M, 2F] = d(gate|up) from sw_gu[M, 2F]
-  int il;
-  AT* act_out;
-  const AT* sw_gu;
-  AT* sw_dgu;
 };
 typedef GemmParamsT<bf16_t> GemmParams;
 typedef GemmParamsT<float> GemmParamsF;
@@ -115,10 +104,10 @@ template <typename AT> int gelu_fwd(hipStream_t st, const AT* x, AT* y, long n);
 template <typename AT> int gelu_bwd(hipStream_t st, const AT* dy, const AT* x, AT* dx, long n);
 template <typename AT> int embed_pos_fwd(hipStream_t st, const int* ids, const int* pos, const AT* E, const AT* P, AT* out, int T, int d, int vocab, int npos);
 template <typename AT> int rope_apply(hipStream_t st, AT* qkv, const int* pos, const float* cosT, const float* sinT, int T, int nheads_rot, int dh, long ld, int backward);
-// il = 0: gu = [gate F | up F]; il = 128: gate and up interleaved in blocks of il columns (see GemmParamsT)
-template <typename AT> int swiglu_fwd(hipStream_t st, const AT* gu, AT* act, int T, int F, int il = 0);
-template <typename AT> int swiglu_bwd(hipStream_t st, const AT* dact, const AT* gu, AT* dgu, int T, int F, int il = 0);
-// SwiGLU fused with the rank-axis contraction that reads its result (swiglu_rank.hip; bf16, il = 0): C[T, N] = alpha * (act | dgu) . B^T, bf16, each row
+// gu = [gate F | up F]
+template <typename AT> int swiglu_fwd(hipStream_t st, const AT* gu, AT* act, int T, int F);
+template <typename AT> int swiglu_bwd(hipStream_t st, const AT* dact, const AT* gu, AT* dgu, int T, int F);
+// SwiGLU fused with the rank-axis contraction that reads its result (swiglu_rank.hip; bf16): C[T, N] = alpha * (act | dgu) . B^T, bf16, each row
 // keeping its slot's block of mask_width columns only (stacked folds; 0 = all N <= 64 columns). forward: B = Ag [N][F]; backward: B = BgT [N][2F]
 struct SwiRank {
   const bf16_t* B; long ldb;
@@ -144,7 +133,7 @@ int rmsnorm_rank_fwd(hipStream_t st, const bf16_t* x, const bf16_t* w, bf16_t* y
 // RMSNorm backward with the norm-weight gradient in the same pass (norm_rank.hip; bf16, the widths of rmsnorm_rank_width_ok): dx as rmsnorm_bwd; dw != null:
 // dw[c] += sum_t dy[t, c] bf16(x[t, c] rstd[t]) through slice sums in ws (colred_ws_floats(T, d) floats) and an ordered finish -- no atomics
 int rmsnorm_bwd_dw(hipStream_t st, const bf16_t* dy, const bf16_t* x, const float* rstd, const bf16_t* w, const bf16_t* dres, bf16_t* dx, float* dw, int T, int d, float* ws);
-bool swiglu_rank_supported(int T, int F, int il, const SwiRank& r);
+bool swiglu_rank_supported(int T, int F, const SwiRank& r);
 int swiglu_rank_fwd(hipStream_t st, const bf16_t* gu, bf16_t* act, int T, int F, const SwiRank& r);
 int swiglu_rank_bwd(hipStream_t st, const bf16_t* dact, const bf16_t* gu, bf16_t* dgu, int T, int F, const SwiRank& r);
 template <typename AT> int logit_rows(hipStream_t st, const float* logits, long ld, const int* target, int n_rows, int V, float* stats, AT* dlogits, long ldd,
@@ -179,8 +168,6 @@ template <typename AT>
 struct LoraGroupDescT {
   int din, dout, r, nseg, RP;     // RP = padded group rank (multiple of 64) = K2 of the fused GEMM segment
   int nmod, nslot;                // nseg = nslot * nmod: segment s = slot * nmod + m (stacked folds: one adapter set per slot)
-  int il;                         // > 0 (gate|up group with interleaved rows): output row n belongs to gate ((n / il) even) or up (odd),
-                                  // logical row (n / (2 il)) * il + n % il; the module with seg_row0 == 0 is gate, the other one up
   int seg_row0[4], seg_row1[4];   // output rows [row0,row1) of the fused projection owned by module m
   long a_off[4 * TST_MAX_STACK], b_off[4 * TST_MAX_STACK];  // offsets of A_seg [r,din] / B_seg [rows,r] in the flat fp32 master/grad buffers
   float scale;                    // alpha / r

@@ -306,35 +306,6 @@ int tst_k_gemm_bench_masked(const void* A, const void* B, void* C, int M, int N,
   return rc;
 }
 
-
-// ---- contraction with a fused SwiGLU epilogue (gate|up interleaved in blocks of 128 columns); variant 5 = the fused 256x256 tile,
-// any other variant = contraction + elementwise kernel
-int tst_k_gemm_swiglu_fwd(const void* A, int64_t lda, const void* B, int64_t ldb, void* gu, void* act, int M, int N, int K, int variant) {
-  GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = (const bf16_t*)A; p.lda = lda; p.B = (const bf16_t*)B; p.ldb = ldb; p.C = gu; p.ldc = N; p.M = M; p.N = N; p.K = K; p.alpha = 1.0f;
-  p.act_out = (bf16_t*)act; p.il = 128;
-  float* slab = nullptr;
-  if (hipMalloc((void**)&slab, 64u << 20) != hipSuccess) return TST_ENOMEM;
-  int rc = gemm_nt(nullptr, p, slab, 64u << 20, variant, -1, nullptr);
-  if (hipDeviceSynchronize() != hipSuccess) rc = TST_EHIP;
-  (void)hipFree(slab);
-  return rc;
-}
-int tst_k_gemm_swiglu_bwd(const void* dy, int64_t lda, const void* WT, int64_t ldb, const void* gu, void* dgu, void* dact_scratch, int M, int F, int K,
-                          int variant) {
-  GemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.A = (const bf16_t*)dy; p.lda = lda; p.B = (const bf16_t*)WT; p.ldb = ldb; p.C = dact_scratch; p.ldc = F; p.M = M; p.N = F; p.K = K; p.alpha = 1.0f;
-  p.sw_gu = (const bf16_t*)gu; p.sw_dgu = (bf16_t*)dgu; p.il = 128;
-  float* slab = nullptr;
-  if (hipMalloc((void**)&slab, 64u << 20) != hipSuccess) return TST_ENOMEM;
-  int rc = gemm_nt(nullptr, p, slab, 64u << 20, variant, -1, nullptr);
-  if (hipDeviceSynchronize() != hipSuccess) rc = TST_EHIP;
-  (void)hipFree(slab);
-  return rc;
-}
-
 // ---- fp32 "strict" kernels
 int tst_k_gemm_f32_nt(const void* A, int64_t lda, const void* B, int64_t ldb, const void* A2, int64_t lda2, const void* B2, int64_t ldb2, void* C, int64_t ldc,
                       const void* R, int64_t ldr, const void* bias, int M, int N, int K, int K2, float alpha) {

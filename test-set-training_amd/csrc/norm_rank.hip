@@ -223,16 +223,17 @@ __global__ __launch_bounds__(NR_NW * 64) void rmsnorm_rank_kernel(NrParams p) {
   }
 }
 
-template <int KS, int RP>
+// RP from nb as rmsnorm_rank_fwd sets p.bm: 16-row blocks (RP = 2) for nb >= 3, 8-row blocks (RP = 1) below
+template <int KS>
 int nr_launch_ks(hipStream_t st, const NrParams& p, int tiles, int nb) {
   const size_t images = (size_t)NR_NW * (1 + nb) * 2048, partial = (size_t)NR_NW * NR_BM * NR_PITCH * sizeof(float);
   const size_t lds = nb ? (images > partial ? images : partial) : 256;
   switch (nb) {
-    case 0: hipLaunchKernelGGL((rmsnorm_rank_kernel<KS, 0, 2, RP>), dim3(tiles), dim3(NR_NW * 64), lds, st, p); break;
-    case 1: hipLaunchKernelGGL((rmsnorm_rank_kernel<KS, 1, 4, RP>), dim3(tiles), dim3(NR_NW * 64), lds, st, p); break;
-    case 2: hipLaunchKernelGGL((rmsnorm_rank_kernel<KS, 2, 4, RP>), dim3(tiles), dim3(NR_NW * 64), lds, st, p); break;
-    case 3: hipLaunchKernelGGL((rmsnorm_rank_kernel<KS, 3, 3, RP>), dim3(tiles), dim3(NR_NW * 64), lds, st, p); break;
-    case 4: hipLaunchKernelGGL((rmsnorm_rank_kernel<KS, 4, 2, RP>), dim3(tiles), dim3(NR_NW * 64), lds, st, p); break;
+    case 0: hipLaunchKernelGGL((rmsnorm_rank_kernel<KS, 0, 2, 1>), dim3(tiles), dim3(NR_NW * 64), lds, st, p); break;
+    case 1: hipLaunchKernelGGL((rmsnorm_rank_kernel<KS, 1, 4, 1>), dim3(tiles), dim3(NR_NW * 64), lds, st, p); break;
+    case 2: hipLaunchKernelGGL((rmsnorm_rank_kernel<KS, 2, 4, 1>), dim3(tiles), dim3(NR_NW * 64), lds, st, p); break;
+    case 3: hipLaunchKernelGGL((rmsnorm_rank_kernel<KS, 3, 3, 2>), dim3(tiles), dim3(NR_NW * 64), lds, st, p); break;
+    case 4: hipLaunchKernelGGL((rmsnorm_rank_kernel<KS, 4, 2, 2>), dim3(tiles), dim3(NR_NW * 64), lds, st, p); break;
     default: return TST_EINVAL;
   }
   return hipGetLastError() == hipSuccess ? TST_OK : TST_EHIP;
@@ -401,10 +402,9 @@ int rmsnorm_rank_fwd(hipStream_t st, const bf16_t* x, const bf16_t* w, bf16_t* y
     p.nslot = 1;
   }
   // rows per workgroup: 8 for the plain norm and rank blocks of <= 32 columns (alone on T = 3555 x 4096: 16.3 / 19.2 us against 18.6 / 19.7 with 16 rows), 16 for
-  // wider blocks, where the 8-row form re-reads twice the Ag bytes and sits at 256 registers (24.2 against 22.9 us). TST_NR_ROWS = 8 / 16 forces one (A/B switch)
-  static const int rows_env = [] { const char* e = getenv("TST_NR_ROWS"); return e ? atoi(e) : 0; }();
-  const int nb_rows = rank ? (p.width ? p.width : p.N) >> 4 : 0;
-  p.bm = rows_env == 16 ? NR_BM : (rows_env == 8 ? 8 : (nb_rows >= 3 ? NR_BM : 8));
+  // wider blocks (nb >= 3 blocks of 16 columns), where the 8-row form re-reads twice the Ag bytes and sits at 256 registers (24.2 against 22.9 us)
+  const int nb = rank ? (p.width ? p.width : p.N) >> 4 : 0;
+  p.bm = nb >= 3 ? NR_BM : 8;
   int tiles = 0;
   for (int s = 0; s < p.nslot; ++s) {
     const int lo = s ? p.ends.t_end[s - 1] : 0, hi = s < p.nslot - 1 ? p.ends.t_end[s] : T;
@@ -414,27 +414,14 @@ int rmsnorm_rank_fwd(hipStream_t st, const bf16_t* x, const bf16_t* w, bf16_t* y
   }
   for (int s = p.nslot; s <= TST_MAX_STACK; ++s) p.tile0[s] = tiles;
   if (tiles == 0) return TST_OK;
-  const int nb = rank ? (p.width ? p.width : p.N) >> 4 : 0;
-  if (p.bm == 8) {
-    switch (d >> 8) {
-      case 1: return nr_launch_ks<1, 1>(st, p, tiles, nb);
-      case 2: return nr_launch_ks<2, 1>(st, p, tiles, nb);
-      case 4: return nr_launch_ks<4, 1>(st, p, tiles, nb);
-      case 8: return nr_launch_ks<8, 1>(st, p, tiles, nb);
-      case 12: return nr_launch_ks<12, 1>(st, p, tiles, nb);
-      case 14: return nr_launch_ks<14, 1>(st, p, tiles, nb);
-      case 16: return nr_launch_ks<16, 1>(st, p, tiles, nb);
-    }
-  } else {
-    switch (d >> 8) {
-      case 1: return nr_launch_ks<1, 2>(st, p, tiles, nb);
-      case 2: return nr_launch_ks<2, 2>(st, p, tiles, nb);
-      case 4: return nr_launch_ks<4, 2>(st, p, tiles, nb);
-      case 8: return nr_launch_ks<8, 2>(st, p, tiles, nb);
-      case 12: return nr_launch_ks<12, 2>(st, p, tiles, nb);
-      case 14: return nr_launch_ks<14, 2>(st, p, tiles, nb);
-      case 16: return nr_launch_ks<16, 2>(st, p, tiles, nb);
-    }
+  switch (d >> 8) {
+    case 1: return nr_launch_ks<1>(st, p, tiles, nb);
+    case 2: return nr_launch_ks<2>(st, p, tiles, nb);
+    case 4: return nr_launch_ks<4>(st, p, tiles, nb);
+    case 8: return nr_launch_ks<8>(st, p, tiles, nb);
+    case 12: return nr_launch_ks<12>(st, p, tiles, nb);
+    case 14: return nr_launch_ks<14>(st, p, tiles, nb);
+    case 16: return nr_launch_ks<16>(st, p, tiles, nb);
   }
   return TST_EINVAL;
 }

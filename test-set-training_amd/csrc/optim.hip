@@ -196,19 +196,11 @@ __global__ __launch_bounds__(256) void adamw_tiled_kernel(float* __restrict__ p,
   }
 }
 
-// which enabled module of the group owns output row n of the fused projection, and which of its rows that is; mod = -1: none.
-// Plain groups: row ranges [seg_row0, seg_row1). Interleaved gate|up group (gd.il > 0): blocks of il rows alternate gate / up.
+// which enabled module of the group owns output row n of the fused projection (row ranges [seg_row0, seg_row1)), and which of its rows that is; mod = -1: none
 template <typename AT>
 __device__ __forceinline__ void row_owner(const LoraGroupDescT<AT>& gd, int n, int& mod, int& local) {
   mod = -1;
   local = 0;
-  if (gd.il > 0) {
-    const int is_up = (n / gd.il) & 1;
-    local = (n / (2 * gd.il)) * gd.il + n % gd.il;
-    for (int s2 = 0; s2 < gd.nmod; ++s2)
-      if ((gd.seg_row0[s2] != 0) == (is_up != 0)) mod = s2;
-    return;
-  }
   for (int s2 = 0; s2 < gd.nmod; ++s2)
     if (n >= gd.seg_row0[s2] && n < gd.seg_row1[s2]) { mod = s2; local = n - gd.seg_row0[s2]; }
 }
@@ -219,35 +211,10 @@ __device__ __forceinline__ void row_owner(const LoraGroupDescT<AT>& gd, int n, i
 //   AgT [din, RP]   AgT[k, seg*r+j] = bf16(scale * A_seg[j, k])   (dX second segment)
 //   Bg  [dout, RP]  Bg[n, seg*r+j]  = B_seg[n - off_seg, j] for rows of segment seg, 0 elsewhere
 //   BgT [RP, dout]  transpose of Bg                                (du = dy.Bg)
-template <typename AT>
-__global__ __launch_bounds__(256) void lora_pack_kernel(const LoraGroupDescT<AT>* __restrict__ descs, const float* __restrict__ master) {
-  const LoraGroupDescT<AT> gd = descs[blockIdx.y];
-  const long nA = (long)gd.RP * gd.din, nB = (long)gd.dout * gd.RP;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nA + nB; i += (long)gridDim.x * 256) {
-    if (i < nA) {
-      const int j = (int)(i / gd.din), k = (int)(i % gd.din);
-      const int seg = j / gd.r, jj = j % gd.r;
-      float v = 0.f;
-      if (seg < gd.nseg) v = master[gd.a_off[seg] + (long)jj * gd.din + k];
-      st1(&gd.Ag[i], v);
-      st1(&gd.AgT[(long)k * gd.RP + j], v * gd.scale);
-    } else {
-      const long e = i - nA;
-      const int n = (int)(e / gd.RP), j = (int)(e % gd.RP);
-      int mod, local;
-      row_owner(gd, n, mod, local);
-      float v = 0.f;
-      const int seg = j / gd.r;   // = slot * nmod + module
-      if (mod >= 0 && seg < gd.nseg && seg % gd.nmod == mod) v = master[gd.b_off[seg] + (long)local * gd.r + j % gd.r];
-      st1(&gd.Bg[e], v);
-      st1(&gd.BgT[(long)j * gd.dout + n], v);
-    }
-  }
-}
-// Tiled form of the pack above (the one the engine launches). grid = (64-wide tiles along the long axis, 2 parts {A, B}, groups); a workgroup packs a
-// 64 x 64 tile per rank chunk. Round 4: a thread owns 8 consecutive elements of a row, so every global access is 16 bytes per lane (the scalar form wrote
-// 2 bytes per lane and ran the 1.5 GB of a Llama-3-8B repack at 1 TB/s: 0.89 ms per optimizer step with nothing of the context to hide it behind); the
-// transposed copies go through a 64 x 64 fp32 LDS tile and leave as whole 16-byte pieces too.
+// grid = (64-wide tiles along the long axis, 2 parts {A, B}, groups); a workgroup packs a 64 x 64 tile per rank chunk. Round 4: a thread owns 8 consecutive
+// elements of a row, so every global access is 16 bytes per lane (the scalar form wrote 2 bytes per lane and ran the 1.5 GB of a Llama-3-8B repack at 1 TB/s:
+// 0.89 ms per optimizer step with nothing of the context to hide it behind); the transposed copies go through a 64 x 64 fp32 LDS tile and leave as whole
+// 16-byte pieces too.
 template <typename AT>
 __global__ __launch_bounds__(256) void lora_pack_tiled_kernel(const LoraGroupDescT<AT>* __restrict__ descs, const float* __restrict__ master) {
   __shared__ float tile[64][65];
@@ -408,18 +375,16 @@ template <typename AT>
 int adamw_step(hipStream_t st, float* p, const float* g, float* m, float* v, long n, const float* clip, float lr, float beta1, float beta2, float eps,
                float wd, float bc1, float bc2_sqrt, AT* shadow) {
   if (n <= 0) return TST_OK;
-  // TST_ADAMW_UNROLL = 1 | 2 | 4 pieces in flight per lane and array, TST_ADAMW_NT = 1 non-temporal accesses (A/B switches; the same arithmetic on the same
-  // elements in every form: bit-identical results)
-  // Defaults: 2 pieces, and non-temporal for the full fine-tune's 30 B/param stream (shadow != nullptr) -- measured on config 3, one GPU, two rounds:
-  // 23.87 QA/s (1, default policy) | 24.29 (1, nt) | 24.51 (2, nt); unrolling alone changes nothing (profiles/r05_full_adamw_ab.txt).
-  static const int unroll = [] { const char* e = getenv("TST_ADAMW_UNROLL"); const int u = e ? atoi(e) : 2; return u == 1 || u == 4 ? u : 2; }();
+  // 2 pieces in flight per lane and array; TST_ADAMW_NT = 1 / 0 non-temporal accesses on / off (A/B switch; the same arithmetic on the same elements in
+  // either form: bit-identical results). Default: non-temporal for the full fine-tune's 30 B/param stream (shadow != nullptr) -- measured on config 3, one GPU,
+  // two rounds: 23.87 QA/s (1 piece, default policy) | 24.29 (1, nt) | 24.51 (2, nt); unrolling alone changes nothing (profiles/r05_full_adamw_ab.txt).
+  constexpr int unroll = 2;
   static const int nt_env = [] { const char* e = getenv("TST_ADAMW_NT"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
   const bool nt = nt_env >= 0 ? nt_env != 0 : shadow != nullptr;
   const dim3 grid(nblocks(((n + 3) / 4 + unroll - 1) / unroll, 8192)), blk(256);
-#define TST_ADAMW_LAUNCH(U, NT) hipLaunchKernelGGL((adamw_kernel<AT, U, NT>), grid, blk, 0, st, p, g, m, v, n, clip, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, shadow)
-  if (unroll == 4) { if (nt) TST_ADAMW_LAUNCH(4, true); else TST_ADAMW_LAUNCH(4, false); }
-  else if (unroll == 2) { if (nt) TST_ADAMW_LAUNCH(2, true); else TST_ADAMW_LAUNCH(2, false); }
-  else { if (nt) TST_ADAMW_LAUNCH(1, true); else TST_ADAMW_LAUNCH(1, false); }
+#define TST_ADAMW_LAUNCH(NT) hipLaunchKernelGGL((adamw_kernel<AT, unroll, NT>), grid, blk, 0, st, p, g, m, v, n, clip, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, shadow)
+  if (nt) TST_ADAMW_LAUNCH(true);
+  else TST_ADAMW_LAUNCH(false);
 #undef TST_ADAMW_LAUNCH
   return hipGetLastError() == hipSuccess ? TST_OK : TST_EHIP;
 }
@@ -427,16 +392,13 @@ template <typename AT>
 int adamw_step_matrix(hipStream_t st, float* p, const float* g, float* m, float* v, int rows, int cols, const float* clip, float lr, float beta1,
                       float beta2, float eps, float wd, float bc1, float bc2_sqrt, AT* shadow, AT* shadowT) {
   if ((rows & 63) || (cols & 63) || !shadow || !shadowT) return TST_EINVAL;
-  // TST_OPT_LDS_KB: extra (unused) dynamic LDS per workgroup = a cap on the workgroups of this kernel a CU holds (A/B switch for the optimizer overlap)
-  static const int pad_kb = [] { const char* e = getenv("TST_OPT_LDS_KB"); return e ? atoi(e) : 0; }();
-  hipLaunchKernelGGL(adamw_tiled_kernel<AT>, dim3((unsigned)((rows >> 6) * (cols >> 6))), dim3(256), (size_t)pad_kb << 10, st, p, g, m, v, rows, cols, clip, lr, beta1, beta2, eps, wd,
+  hipLaunchKernelGGL(adamw_tiled_kernel<AT>, dim3((unsigned)((rows >> 6) * (cols >> 6))), dim3(256), 0, st, p, g, m, v, rows, cols, clip, lr, beta1, beta2, eps, wd,
                      bc1, bc2_sqrt, shadow, shadowT);
   return hipGetLastError() == hipSuccess ? TST_OK : TST_EHIP;
 }
 template <typename AT>
 int lora_pack(hipStream_t st, const LoraGroupDescT<AT>* descs_dev, int ngroups, const float* master, long max_long_axis) {
   if (ngroups <= 0) return TST_OK;
-  (void)lora_pack_kernel<AT>;  // element-wise reference form, kept for documentation of the layout
   hipLaunchKernelGGL(lora_pack_tiled_kernel<AT>, dim3((unsigned)((max_long_axis + 63) / 64), 2, ngroups), dim3(256), 0, st, descs_dev, master);
   return hipGetLastError() == hipSuccess ? TST_OK : TST_EHIP;
 }

@@ -276,7 +276,7 @@ int sr_launch_nw(hipStream_t st, int mode, const SrParams& p, int tiles, int nb)
 }
 
 int sr_launch(hipStream_t st, int mode, const bf16_t* gu, const bf16_t* dact, bf16_t* out, int T, int F, const SwiRank& r) {
-  if (!swiglu_rank_supported(T, F, 0, r)) return TST_EINVAL;
+  if (!swiglu_rank_supported(T, F, r)) return TST_EINVAL;
   SrParams p;
   p.gu = gu; p.dact = dact; p.out = out; p.B = r.B; p.ldb = r.ldb; p.C = r.C;
   p.M = T; p.N = r.N; p.F = F; p.alpha = r.alpha;
@@ -310,8 +310,8 @@ int sr_launch(hipStream_t st, int mode, const bf16_t* gu, const bf16_t* dact, bf
 
 }  // namespace
 
-bool swiglu_rank_supported(int T, int F, int il, const SwiRank& r) {
-  if (T <= 0 || il != 0 || (F & 63) || (F >> 6) < 4 || !r.B || !r.C || (r.ldb & 7) || r.N < 16 || (r.N & 15)) return false;
+bool swiglu_rank_supported(int T, int F, const SwiRank& r) {
+  if (T <= 0 || (F & 63) || (F >> 6) < 4 || !r.B || !r.C || (r.ldb & 7) || r.N < 16 || (r.N & 15)) return false;
   if (r.mask_width) return (r.mask_width & 15) == 0 && r.mask_width <= 64 && r.mask_nslot >= 1 && r.mask_nslot <= TST_MAX_STACK && r.mask_nslot * r.mask_width <= r.N;
   return r.N <= 64;
 }

@@ -179,8 +179,6 @@ LAB_SIGNATURES = {
     "tst_k_gemm_pp_stamps": (C.c_int, [_P]),
     "tst_k_gemm_bench": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F)]),
     "tst_k_gemm_bench_masked": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F)]),
-    "tst_k_gemm_swiglu_fwd": (C.c_int, [_P, _L, _P, _L, _P, _P, _I, _I, _I, _I]),
-    "tst_k_gemm_swiglu_bwd": (C.c_int, [_P, _L, _P, _L, _P, _P, _P, _I, _I, _I, _I]),
     "tst_k_gemm_f32_nt": (C.c_int, [_P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _L, _P, _I, _I, _I, _I, _F]),
     "tst_k_gemm_f32_tn": (C.c_int, [_P, _L, _P, _L, _P, _L, _I, _I, _I, _F]),
     "tst_k_attn_fwd_f32": (C.c_int, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _I, _F]),

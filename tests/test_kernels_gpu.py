@@ -902,50 +902,40 @@ def test_adamw_clip(L, golden_dir):
         assert_close(f"adamw_step{s + 1}_vs_torch_fused", p_.get(np.float32, (n,)), g["ad_p"][s], 2e-6, 1e-6)
 
 
-def _il(cols_gate, cols_up, il=128):
-    """[.., F] gate and up -> interleaved [.., 2F] (blocks of il gate columns, then il up columns)"""
-    F = cols_gate.shape[-1]
-    out = np.empty(cols_gate.shape[:-1] + (2 * F,), cols_gate.dtype)
-    for b in range(F // il):
-        out[..., 2 * b * il: 2 * b * il + il] = cols_gate[..., b * il:(b + 1) * il]
-        out[..., 2 * b * il + il: 2 * (b + 1) * il] = cols_up[..., b * il:(b + 1) * il]
-    return out
-
-
 @pytest.mark.parametrize("M,F,K", [(300, 256, 128), (1200, 512, 256), (257, 1024, 64)])
-def test_fused_swiglu_epilogues_match_the_unfused_path_bit_for_bit(L, M, F, K):
-    """SwiGLU in the contraction epilogue (256x256 ping-pong tile, gate|up interleaved in 128-column blocks): forward act and backward
-    d(gate|up) are bit-identical to contraction + elementwise kernel (same arithmetic on the same bf16-rounded values), and both follow
-    the oracle's swiglu."""
+def test_swiglu_behind_both_tile_families_is_bit_identical(L, M, F, K):
+    """gate|up projection ([gate | up]) and the down projection's dX on the 256x256 ping-pong tile (variant 5) and on the 128x128 tile (variant 0),
+    each followed by the elementwise SwiGLU kernel: the two tile families give bit-identical results, and both follow the oracle's swiglu."""
     rng = np.random.default_rng(M + F + K)
     lib = L.load_lab()
     x = O.rbf(rng.standard_normal((M, K)).astype(np.float32))
     Wg, Wu = (O.rbf(0.2 * rng.standard_normal((F, K)).astype(np.float32)) for _ in range(2))
-    Wgu = _il(Wg.T, Wu.T).T.copy()                   # rows interleaved
-    x_, W_ = L.dev_bf16(x), L.dev_bf16(Wgu)
+    x_, W_ = L.dev_bf16(x), L.dev_bf16(np.concatenate([Wg, Wu], 0))
     outs = {}
-    for v in (5, 0):
+    for v, sk in ((5, 1), (0, -1)):
         gu_, act_ = L.DevBuf(nbytes=M * 2 * F * 2), L.DevBuf(nbytes=M * F * 2)
-        assert lib.tst_k_gemm_swiglu_fwd(x_.ptr, K, W_.ptr, K, gu_.ptr, act_.ptr, M, 2 * F, K, v) == 0
+        assert lib.tst_k_gemm_nt(x_.ptr, K, W_.ptr, K, None, 0, None, 0, gu_.ptr, 2 * F, None, 0, M, 2 * F, K, 0, 1.0, 0, v, sk) == 0
+        assert lib.tst_k_swiglu_fwd(gu_.ptr, act_.ptr, M, F) == 0
         outs[v] = (gu_.get(np.uint16, (M, 2 * F)), act_.get(np.uint16, (M, F)))
     np.testing.assert_array_equal(outs[5][0], outs[0][0])
     np.testing.assert_array_equal(outs[5][1], outs[0][1])
     g_ref, u_ref = O.rbf(x @ Wg.T), O.rbf(x @ Wu.T)
     act_ref = O.swiglu_fwd(g_ref, u_ref, bf16=True)
     from tst.lib import from_bf16_bits
-    assert_close(f"fused_swiglu_fwd M{M} F{F}", from_bf16_bits(outs[5][1]), act_ref, 2 * BF_ULP, 1e-3)
+    assert_close(f"swiglu_fwd behind the tile M{M} F{F}", from_bf16_bits(outs[5][1]), act_ref, 2 * BF_ULP, 1e-3)
     # backward: dy [M, Kd] . WdT [F, Kd]^T -> d(act) -> d(gate|up)
     Kd = K
     dy = O.rbf(rng.standard_normal((M, Kd)).astype(np.float32))
     WdT = O.rbf(0.2 * rng.standard_normal((F, Kd)).astype(np.float32))
-    gu = from_bf16_bits(outs[5][0])
     dy_, WdT_, gu_ = L.dev_bf16(dy), L.dev_bf16(WdT), L.DevBuf(outs[5][0])
     res = {}
-    for v in (5, 0):
-        dgu_, scr_ = L.DevBuf(nbytes=M * 2 * F * 2), L.DevBuf(nbytes=M * F * 2)
-        assert lib.tst_k_gemm_swiglu_bwd(dy_.ptr, Kd, WdT_.ptr, Kd, gu_.ptr, dgu_.ptr, scr_.ptr, M, F, Kd, v) == 0
+    for v, sk in ((5, 1), (0, -1)):
+        dgu_, dact_ = L.DevBuf(nbytes=M * 2 * F * 2), L.DevBuf(nbytes=M * F * 2)
+        assert lib.tst_k_gemm_nt(dy_.ptr, Kd, WdT_.ptr, Kd, None, 0, None, 0, dact_.ptr, F, None, 0, M, F, Kd, 0, 1.0, 0, v, sk) == 0
+        assert lib.tst_k_swiglu_bwd(dact_.ptr, gu_.ptr, dgu_.ptr, M, F) == 0
         res[v] = dgu_.get(np.uint16, (M, 2 * F))
     np.testing.assert_array_equal(res[5], res[0])
     dact = O.rbf(dy @ WdT.T)
     dg_ref, du_ref = O.swiglu_bwd(dact, g_ref, u_ref, bf16=True)
-    assert_close(f"fused_swiglu_bwd M{M} F{F}", from_bf16_bits(res[5]), _il(dg_ref, du_ref), 4 * BF_ULP, 2e-3)
+    for v in (5, 0):
+        assert_close(f"swiglu_bwd behind the tile M{M} F{F} variant {v}", from_bf16_bits(res[v]), np.concatenate([dg_ref, du_ref], 1), 4 * BF_ULP, 2e-3)
