@@ -55,6 +55,12 @@ extern "C" {
  * use in full fine-tune. LoRA targets: Q|K|V -> attn.c_attn, O -> attn.c_proj, GATE|UP -> mlp.c_fc, DOWN -> mlp.c_proj.
  * The vocabulary need not be a multiple of 64 (50257): it is padded internally, logits_out stays [n_rows, vocab]. */
 #define TST_ARCH_GPT2 2
+/* Qwen3 (dense): the Llama layer without q/k/v bias plus an RMSNorm over head_dim on every query head and every key head, behind the projection and before
+ * RoPE (modeling_qwen3.py:237-238 q_norm / k_norm = Qwen3RMSNorm(head_dim), :252-253 q_norm(q_proj(x).view(.., head_dim)), k_norm(...)); eps = rms_norm_eps.
+ * Two more weights per layer, "model.layers.N.self_attn.q_norm.weight" and "...k_norm.weight" ([head_dim] each, shared by all query resp. key heads):
+ * tst_finalize_weights fails with TST_ESTATE while one is missing; a full fine-tune trains them in the no-decay group (trainer.py:1313 excludes "_norm").
+ * head_dim 128; num_heads * head_dim need not equal hidden_size. Not built: sliding-window layers, attention_bias, the MoE variant. */
+#define TST_ARCH_QWEN3 3
 
 #define TST_TRAIN_LORA 0
 #define TST_TRAIN_FULL 1   /* every weight trainable (BASELINE config 3): fp32 master/grad/moments for all parameters */

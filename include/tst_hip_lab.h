@@ -66,6 +66,16 @@ int tst_k_rmsnorm_rank_fwd(const void* x, const void* w, void* y, float* rstd, i
                            int mask_width, int mask_nslot, const int32_t* t_end);
 int tst_k_rmsnorm_bwd(const void* dy, const void* x, const float* rstd, const void* w, const void* dres, void* dx, int T, int d);
 int tst_k_rope(void* qkv, const int32_t* pos, const float* cosT, const float* sinT, int T, int nheads_rot, int dh, int64_t ld, int backward);
+/* Qwen3 per-head q/k RMSNorm (csrc/head_norm.hip), in place on the first (H + Hkv) * 128 columns of qkv / dqkv [T, ld]: the H query heads take wq [128], the Hkv
+ * key heads wk [128]; the v columns are not touched. rstd: fp32 [T, H + Hkv]. stash [T, H + Hkv, 128]: the raw rows (forward: written when non-NULL; backward:
+ * required). pos / cosT / sinT non-NULL: the rotation of tst_k_rope in the same pass (forward: norm then rotate; backward: un-rotate then norm backward),
+ * bit-identical to the two passes. dwq / dwk (device fp32 [128], both or neither) += the weight gradients (partial sums + ordered finish, no atomics); they need
+ * ws, a caller-owned device scratch of TST_HEAD_NORM_WS_FLOATS floats (NULL otherwise). */
+#define TST_HEAD_NORM_WS_FLOATS (1024 * 256)
+int tst_k_head_norm_fwd(void* qkv, int64_t ld, const void* wq, const void* wk, float* rstd, void* stash, int T, int H, int Hkv, float eps, const int32_t* pos,
+                        const float* cosT, const float* sinT);
+int tst_k_head_norm_bwd(void* dqkv, int64_t ld, const void* wq, const void* wk, const float* rstd, const void* stash, int T, int H, int Hkv, const int32_t* pos,
+                        const float* cosT, const float* sinT, float* dwq, float* dwk, float* ws);
 int tst_k_swiglu_fwd(const void* gu, void* act, int T, int F);
 int tst_k_swiglu_bwd(const void* dact, const void* gu, void* dgu, int T, int F);
 /* SwiGLU fused with the rank-axis contraction that reads its result (csrc/swiglu_rank.hip): act / dgu as above AND us[T,N] = alpha act . Ag^T (Ag [N][F]) resp.
@@ -119,6 +129,10 @@ int tst_k_attn_bwd_f32(const void* qkv, int64_t ld, const void* out, int64_t ldo
 int tst_k_rmsnorm_fwd_f32(const void* x, const void* w, void* y, float* rstd, int T, int d, float eps);
 int tst_k_rmsnorm_bwd_f32(const void* dy, const void* x, const float* rstd, const void* w, const void* dres, void* dx, int T, int d);
 int tst_k_rope_f32(void* qkv, const int32_t* pos, const float* cosT, const float* sinT, int T, int nheads_rot, int dh, int64_t ld, int backward);
+int tst_k_head_norm_fwd_f32(void* qkv, int64_t ld, const void* wq, const void* wk, float* rstd, void* stash, int T, int H, int Hkv, float eps, const int32_t* pos,
+                            const float* cosT, const float* sinT);
+int tst_k_head_norm_bwd_f32(void* dqkv, int64_t ld, const void* wq, const void* wk, const float* rstd, const void* stash, int T, int H, int Hkv, const int32_t* pos,
+                            const float* cosT, const float* sinT, float* dwq, float* dwk, float* ws);
 int tst_k_swiglu_fwd_f32(const void* gu, void* act, int T, int F);
 int tst_k_swiglu_bwd_f32(const void* dact, const void* gu, void* dgu, int T, int F);
 

@@ -117,6 +117,11 @@ template <typename AT>
 struct LayerT {
   AT *attn_norm, *mlp_norm;
   AT* bqkv = nullptr;  // Qwen2 / GPT-2: bias of the fused q|k|v projection [dqkv]
+  // Qwen3: per-head RMSNorm of q and k over head_dim (modeling_qwen3.py:237-238, 252-253): one [128] vector for all query heads, one for all key heads
+  AT *q_norm = nullptr, *k_norm = nullptr;
+  bool q_norm_set = false, k_norm_set = false;   // tst_finalize_weights refuses a Qwen3 context whose head-norm vectors were never given
+  AT* qk_raw = nullptr;        // stash [T, (H + Hkv) 128]: q|k as the projection wrote them (the head norm runs in place; its backward re-forms x_hat from this)
+  float* rstd_qk = nullptr;    // [T, H + Hkv]
   AT *attn_norm_b = nullptr, *mlp_norm_b = nullptr, *bo = nullptr, *bgu = nullptr, *bd = nullptr;  // GPT-2: LayerNorm and Conv1D biases
   AT *Wqkv, *WqkvT, *Wo, *WoT, *Wgu, *WguT, *Wd, *WdT;
   LoraGroupT<AT> g_qkv, g_o, g_gu, g_d;
@@ -198,6 +203,8 @@ struct tst_ctx {
   bool opt_pending = false;
   bool opt_overlap = env_flag("TST_OPT_OVERLAP", true);   // "opt_overlap" (tst_set_option)
   bool gpt2 = false;
+  bool qk_norm = false;    // TST_ARCH_QWEN3: head norm between the q|k|v projection and RoPE (csrc/head_norm.hip)
+  float* hn_ws = nullptr;  // full fine-tune: partial sums of the head-norm weight gradients (HEAD_NORM_WS_FLOATS)
   int Vp = 0;    // vocabulary padded to a multiple of 64 (GPT-2: 50257 -> 50304): row count of embed / lm_head, ld of the logits
   int Fgu = 0;   // output width of the first MLP projection: 2F (gate|up) or F (c_fc)
   int npos = 0;  // rows of wpe
@@ -936,6 +943,13 @@ int forward(CtxT<AT>* ctx, bool stash) {
     // RoPE: inside the attention kernels where they can (bf16 path, sequences <= 128 tokens: q and k then stay UN-rotated in the stash and
     // the backward kernel rotates dq / dk back itself), else as a pass of its own over q and k
     const bool rope_in = !ctx->gpt2 && rope_fused(ctx);
+    if (ctx->qk_norm) {
+      // Qwen3: head norm in place on q|k, and the rotation in the same traversal whenever RoPE is a pass of its own (q|k read and written once, not twice)
+      const int slot = prof_begin(ctx, st, ctx->prof_hbm);
+      CTX_RC(head_norm_fwd<AT>(st, A.qkv, ctx->dqkv, W.q_norm, W.k_norm, A.rstd_qk, stash ? A.qk_raw : nullptr, T, ctx->H, ctx->Hkv, ctx->cfg.rms_norm_eps,
+                               rope_in ? nullptr : ctx->d_pos, ctx->cosT, ctx->sinT));
+      prof_end(ctx, st, slot, PROF_NORM, 1, (stash ? 3.0 : 2.0) * T * (ctx->dq + ctx->dkv) * sizeof(AT));
+    } else
     if (!ctx->gpt2 && !rope_in) CTX_RC(rope_apply<AT>(st, A.qkv, ctx->d_pos, ctx->cosT, ctx->sinT, T, ctx->H + ctx->Hkv, ctx->dh, ctx->dqkv, 0));
     {
       const int slot = prof_begin(ctx, st, ctx->prof_hbm);
@@ -1218,6 +1232,13 @@ int backward(CtxT<AT>* ctx, int num_items) {
     else
     CTX_RC(attn_bwd(st, W.qkv, ctx->dqkv, W.attn, ctx->dattn, ctx->dattn_b, ctx->dattn, W.lse, ctx->delta, ctx->d_cu, ctx->cur_S, ctx->cur_maxlen,
                     ctx->dqkv_b, T, ctx->H, ctx->Hkv, ctx->dh, scale));
+    if (ctx->qk_norm) {
+      // Qwen3: (un-rotate,) head-norm backward in place on dq|dk; a full fine-tune takes the two weight gradients in the same pass
+      const int slot = prof_begin(ctx, st, ctx->prof_hbm);
+      CTX_RC(head_norm_bwd<AT>(st, ctx->dqkv_b, ctx->dqkv, W.q_norm, W.k_norm, W.rstd_qk, W.qk_raw, T, ctx->H, ctx->Hkv, rope_in ? nullptr : ctx->d_pos, ctx->cosT,
+                               ctx->sinT, full ? gof(W.q_norm) : nullptr, full ? gof(W.k_norm) : nullptr, ctx->hn_ws));
+      prof_end(ctx, st, slot, PROF_NORM, 1, 3.0 * T * (ctx->dq + ctx->dkv) * sizeof(AT));
+    } else
     if (!ctx->gpt2 && !rope_in) CTX_RC(rope_apply<AT>(st, ctx->dqkv_b, ctx->d_pos, ctx->cosT, ctx->sinT, T, ctx->H + ctx->Hkv, ctx->dh, ctx->dqkv, 1));
     if (full && W.bqkv) CTX_RC(colsum<AT>(st, ctx->dqkv_b, ctx->dqkv, gof(W.bqkv), T, ctx->dqkv, ctx->colred_ws));
     // LoRA: the embedding is frozen, so the gradient of layer 0's INPUT has no reader: its q|k|v projection's dX contraction and the norm backward behind it are skipped
@@ -1377,6 +1398,8 @@ WeightRefT<AT> find_weight(CtxT<AT>* ctx, const char* name) {
   else if (s == "self_attn.k_proj.weight") { r.ptr = W.Wqkv + (int64_t)ctx->dq * d; r.numel = (int64_t)ctx->dkv * d; }
   else if (s == "self_attn.v_proj.weight") { r.ptr = W.Wqkv + (int64_t)(ctx->dq + ctx->dkv) * d; r.numel = (int64_t)ctx->dkv * d; }
   else if (s == "self_attn.o_proj.weight") { r.ptr = W.Wo; r.numel = (int64_t)d * ctx->dattn; }
+  else if (W.q_norm && s == "self_attn.q_norm.weight") { r.ptr = W.q_norm; r.numel = ctx->dh; }
+  else if (W.k_norm && s == "self_attn.k_norm.weight") { r.ptr = W.k_norm; r.numel = ctx->dh; }
   else if (W.bqkv && s == "self_attn.q_proj.bias") { r.ptr = W.bqkv; r.numel = ctx->dq; }
   else if (W.bqkv && s == "self_attn.k_proj.bias") { r.ptr = W.bqkv + ctx->dq; r.numel = ctx->dkv; }
   else if (W.bqkv && s == "self_attn.v_proj.bias") { r.ptr = W.bqkv + ctx->dq + ctx->dkv; r.numel = ctx->dkv; }
@@ -1392,6 +1415,7 @@ int build_ctx(CtxT<AT>* ctx) {
   ctx->d = c.hidden_size; ctx->L = c.num_layers; ctx->H = c.num_heads; ctx->Hkv = c.num_kv_heads; ctx->dh = c.head_dim;
   ctx->F = c.intermediate_size; ctx->V = c.vocab_size;
   ctx->gpt2 = (c.arch == TST_ARCH_GPT2);
+  ctx->qk_norm = (c.arch == TST_ARCH_QWEN3);
   ctx->Vp = roundup(ctx->V, 64);
   ctx->Fgu = ctx->gpt2 ? ctx->F : 2 * ctx->F;
   ctx->npos = c.max_position;
@@ -1402,7 +1426,8 @@ int build_ctx(CtxT<AT>* ctx) {
   // masked in-kernel but must be readable and finite, hence the zero fill below)
   const int d = ctx->d, F = ctx->F, V = ctx->Vp, L = ctx->L, T = ctx->Tpad_max, Tp = ctx->Tpad_max, Fgu = ctx->Fgu;
   const bool gpt2 = ctx->gpt2;
-  if (c.arch != TST_ARCH_LLAMA && c.arch != TST_ARCH_QWEN2 && !gpt2) return fail(ctx, TST_EINVAL, "unsupported arch");
+  if (c.arch != TST_ARCH_LLAMA && c.arch != TST_ARCH_QWEN2 && c.arch != TST_ARCH_QWEN3 && !gpt2) return fail(ctx, TST_EINVAL, "unsupported arch");
+  const bool qk_norm = ctx->qk_norm;
   const bool qkv_bias = (c.arch == TST_ARCH_QWEN2) || gpt2;
   if (gpt2 && ctx->Hkv != ctx->H) return fail(ctx, TST_EINVAL, "GPT-2: num_kv_heads must equal num_heads");
   if (gpt2 && ctx->dq != ctx->d) return fail(ctx, TST_EINVAL, "GPT-2: num_heads * head_dim must equal hidden_size");
@@ -1456,7 +1481,7 @@ int build_ctx(CtxT<AT>* ctx) {
     // GPT-2: one tied [V, d] matrix + wpe; per layer 2 LayerNorms with bias and 4 Conv1D biases, + ln_f
     ctx->n_decay = (gpt2 ? (int64_t)V * d + (int64_t)ctx->npos * d : 2 * (int64_t)V * d) + L * per_layer;
     ctx->n_train = ctx->n_decay + (gpt2 ? (int64_t)L * (4 * d + ctx->dqkv + d + Fgu + d) + 2 * d
-                                         : (int64_t)(2 * L + 1) * d + (qkv_bias ? (int64_t)L * ctx->dqkv : 0));
+                                         : (int64_t)(2 * L + 1) * d + (qkv_bias ? (int64_t)L * ctx->dqkv : 0) + (qk_norm ? (int64_t)L * 2 * ctx->dh : 0));
     if (ctx->zero_on) {
       const tsthost::ZeroShard z = tsthost::zero_shard(ctx->n_train, ctx->zero, ctx->zero_rank);   // (host_logic.h)
       ctx->n_pad = z.n_pad; ctx->z_shard = z.shard; ctx->z_lo = z.lo; ctx->z_hi = z.hi;
@@ -1525,11 +1550,13 @@ int build_ctx(CtxT<AT>* ctx) {
     } else if (sh) {
       const LayerT<AT>& S = sh->layers[l];
       W.attn_norm = S.attn_norm; W.mlp_norm = S.mlp_norm; W.bqkv = S.bqkv;
+      W.q_norm = S.q_norm; W.k_norm = S.k_norm;
       W.attn_norm_b = S.attn_norm_b; W.mlp_norm_b = S.mlp_norm_b; W.bo = S.bo; W.bgu = S.bgu; W.bd = S.bd;
       W.Wqkv = S.Wqkv; W.WqkvT = S.WqkvT; W.Wo = S.Wo; W.WoT = S.WoT; W.Wgu = S.Wgu; W.WguT = S.WguT; W.Wd = S.Wd; W.WdT = S.WdT;
     } else {
       ALLOC(W.attn_norm, AT, d); ALLOC(W.mlp_norm, AT, d);
       if (qkv_bias) ALLOC(W.bqkv, AT, ctx->dqkv);
+      if (qk_norm) { ALLOC(W.q_norm, AT, ctx->dh); ALLOC(W.k_norm, AT, ctx->dh); }
       if (gpt2) {
         ALLOC(W.attn_norm_b, AT, d); ALLOC(W.mlp_norm_b, AT, d);
         ALLOC(W.bo, AT, d); ALLOC(W.bgu, AT, Fgu); ALLOC(W.bd, AT, d);
@@ -1568,6 +1595,7 @@ int build_ctx(CtxT<AT>* ctx) {
     ALLOC(W.attn, AT, (int64_t)T * ctx->dattn); ALLOC(W.hmid, AT, (int64_t)T * d); ALLOC(W.xn2, AT, (int64_t)T * d);
     ALLOC(W.gu, AT, (int64_t)T * Fgu); ALLOC(W.act, AT, (int64_t)T * F);
     ALLOC(W.rstd1, float, 2 * T); ALLOC(W.rstd2, float, 2 * T); ALLOC(W.lse, float, (int64_t)ctx->H * T);  // LayerNorm keeps {mean, rstd}
+    if (qk_norm) { ALLOC(W.qk_raw, AT, (int64_t)T * (ctx->dq + ctx->dkv)); ALLOC(W.rstd_qk, float, (int64_t)T * (ctx->H + ctx->Hkv)); }
     W.us_qkv = W.us_o = W.us_gu = W.us_d = nullptr;
     if (W.g_qkv.on) ALLOC(W.us_qkv, AT, (int64_t)T * W.g_qkv.d.RP);
     if (W.g_o.on) ALLOC(W.us_o, AT, (int64_t)T * W.g_o.d.RP);
@@ -1606,6 +1634,12 @@ int build_ctx(CtxT<AT>* ctx) {
         reg(pre + "self_attn.q_proj.bias", b, 1, ctx->dq);
         reg(pre + "self_attn.k_proj.bias", b + ctx->dq, 1, ctx->dkv);
         reg(pre + "self_attn.v_proj.bias", b + ctx->dq + ctx->dkv, 1, ctx->dkv);
+      }
+      if (qk_norm) {   // Qwen3 head-norm vectors: with the other norm vectors in the no-decay tail (HF's Trainer excludes every "_norm" parameter from decay)
+        ctx->layers[l].q_norm = take(ctx->dh);
+        reg(pre + "self_attn.q_norm.weight", ctx->layers[l].q_norm, 1, ctx->dh);
+        ctx->layers[l].k_norm = take(ctx->dh);
+        reg(pre + "self_attn.k_norm.weight", ctx->layers[l].k_norm, 1, ctx->dh);
       }
     }
     ctx->final_norm = take(d);
@@ -1764,6 +1798,7 @@ int build_ctx(CtxT<AT>* ctx) {
   if (ctx->full) {   // transposed activations for the weight-gradient contractions
     ALLOC(ctx->colred_ws, float, 2 * colred_ws_floats(T, dout_max > d ? dout_max : d));
     ALLOC(ctx->colred_ws_side, float, 2 * colred_ws_floats(T, d));
+    if (qk_norm) ALLOC(ctx->hn_ws, float, HEAD_NORM_WS_FLOATS);
     for (auto& e : ctx->ev_ndw) CTX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     if (!(ctx->kmajor & 2)) {   // (else dW = dy^T . x on the TN member: no transposed copies)
       ALLOC(ctx->dyT, AT, (int64_t)dout_max * T);
@@ -1871,6 +1906,11 @@ int set_weight_impl(CtxT<AT>* ctx, const char* name, const void* host, int dtype
     src = tmp.data();
   }
   CTX_HIP(hipMemcpy(w.ptr, src, (size_t)numel * sizeof(AT), hipMemcpyHostToDevice));
+  if (ctx->qk_norm)
+    for (auto& W : ctx->layers) {
+      if (w.ptr == W.q_norm) W.q_norm_set = true;
+      if (w.ptr == W.k_norm) W.k_norm_set = true;
+    }
   return TST_OK;
 }
 
@@ -1898,6 +1938,10 @@ int get_weight_impl(CtxT<AT>* ctx, const char* name, float* host_out, int64_t nu
 template <typename AT>
 int finalize_weights_impl(CtxT<AT>* ctx) {
   if (ctx->parent) return fail(ctx, TST_ESTATE, "a forked context borrows its parent's weights");
+  if (ctx->qk_norm)
+    for (size_t l = 0; l < ctx->layers.size(); ++l)
+      if (!ctx->layers[l].q_norm_set || !ctx->layers[l].k_norm_set)
+        return fail(ctx, TST_ESTATE, "Qwen3: model.layers." + std::to_string(l) + ".self_attn.q_norm.weight / k_norm.weight were not set");
   CTX_HIP(hipDeviceSynchronize());  // tst_set_weight copies (default stream) must have landed
   hipStream_t st = ctx->stream;
   CTX_RC(refresh_transposes(ctx));
@@ -1931,6 +1975,10 @@ int init_random_impl(CtxT<AT>* ctx, uint64_t seed, float stdv) {
     CTX_RC(fill_const<AT>(st, W.attn_norm, d, 1.0f));
     CTX_RC(fill_const<AT>(st, W.mlp_norm, d, 1.0f));
     if (W.bqkv) CTX_RC(fill_const<AT>(st, W.bqkv, ctx->dqkv, 0.0f));
+    if (ctx->qk_norm) {
+      CTX_RC(fill_const<AT>(st, W.q_norm, ctx->dh, 1.0f)); CTX_RC(fill_const<AT>(st, W.k_norm, ctx->dh, 1.0f));
+      W.q_norm_set = W.k_norm_set = true;
+    }
     if (ctx->gpt2) {
       CTX_RC(fill_const<AT>(st, W.attn_norm_b, d, 0.0f)); CTX_RC(fill_const<AT>(st, W.mlp_norm_b, d, 0.0f));
       CTX_RC(fill_const<AT>(st, W.bo, d, 0.0f)); CTX_RC(fill_const<AT>(st, W.bgu, ctx->Fgu, 0.0f)); CTX_RC(fill_const<AT>(st, W.bd, d, 0.0f));

@@ -66,17 +66,21 @@ inline DecaySplit decay_split(int64_t lo, int64_t hi, int64_t n_decay) {
 
 // ------------------------------------------------------------------------------------------------ flat layout of a full fine-tune
 // ONE flat vector in the order [token embedding | (GPT-2: learned positions) | per layer Wqkv, Wo, Wgu, Wd | (Llama / Qwen2: lm_head) | norm vectors and
-// biases]: matrices first (= HF's decay group), vectors last. `regions` = the gradient regions in the order backward finishes them: lm_head (untied),
+// biases (Qwen3: and the q_norm / k_norm head-norm vectors, per layer behind its two norm vectors)]: matrices first (= HF's decay group), vectors last. `regions` = the gradient regions in the order backward finishes them: lm_head (untied),
 // layers L-1 .. 0, the embedding side, the vector tail -- the units of the region-wise data-parallel reduction.
 struct ModelDims {
   int d, L, F, Fgu, V /* padded to 64 */, dq, dkv, dqkv, dattn, npos;
   bool gpt2, qkv_bias;
+  bool qk_norm;   // Qwen3: two [dh] head-norm vectors per layer
+  int dh;
 };
 inline ModelDims model_dims(const tst_model_cfg& c) {
   ModelDims m;
   m.d = c.hidden_size; m.L = c.num_layers; m.F = c.intermediate_size;
   m.gpt2 = c.arch == TST_ARCH_GPT2;
   m.qkv_bias = c.arch == TST_ARCH_QWEN2 || m.gpt2;
+  m.qk_norm = c.arch == TST_ARCH_QWEN3;
+  m.dh = c.head_dim;
   m.V = roundup(c.vocab_size, 64);
   m.Fgu = m.gpt2 ? m.F : 2 * m.F;
   m.npos = c.max_position;
@@ -94,7 +98,7 @@ inline FullLayout full_layout(const ModelDims& m) {
   const int64_t V = m.V, d = m.d;
   f.per_layer = (int64_t)m.dqkv * d + (int64_t)d * m.dattn + (int64_t)m.Fgu * d + (int64_t)d * m.F;
   f.n_decay = (m.gpt2 ? V * d + (int64_t)m.npos * d : 2 * V * d) + m.L * f.per_layer;
-  f.n_train = f.n_decay + (m.gpt2 ? (int64_t)m.L * (4 * d + m.dqkv + d + m.Fgu + d) + 2 * d : (int64_t)(2 * m.L + 1) * d + (m.qkv_bias ? (int64_t)m.L * m.dqkv : 0));
+  f.n_train = f.n_decay + (m.gpt2 ? (int64_t)m.L * (4 * d + m.dqkv + d + m.Fgu + d) + 2 * d : (int64_t)(2 * m.L + 1) * d + (m.qkv_bias ? (int64_t)m.L * m.dqkv : 0) + (m.qk_norm ? (int64_t)m.L * 2 * m.dh : 0));
   int64_t o = 0;
   f.embed = o; o += V * d;
   if (m.gpt2) { f.wpe = o; o += (int64_t)m.npos * d; }

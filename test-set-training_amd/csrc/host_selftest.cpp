@@ -180,7 +180,14 @@ static void test_zero_and_layout() {
   const tst_model_cfg g2 = cfg(TST_ARCH_GPT2, 50257, 768, 12, 12, 12, 64, 3072, 1024);
   const FullLayout gl = full_layout(model_dims(g2));
   CHECK(gl.n_train == 124439808LL + (50304LL - 50257LL) * 768);   // the vocabulary is padded to a multiple of 64 with zero rows
-  for (const FullLayout* f : {&l3, &q7, &gl}) {
+  // Qwen3-8B (8,190,735,360): no q/k/v bias, two [128] head-norm vectors per layer in the no-decay tail
+  const FullLayout q3 = full_layout(model_dims(cfg(TST_ARCH_QWEN3, 151936, 4096, 36, 32, 8, 128, 12288, 128)));
+  CHECK(q3.n_train == 8190735360LL);
+  CHECK(q3.n_train - q3.n_decay == (2LL * 36 + 1) * 4096 + 36LL * 2 * 128);
+  // Qwen3-0.6B's widths: num_heads * head_dim (2048) != hidden_size (1024)
+  const FullLayout q06 = full_layout(model_dims(cfg(TST_ARCH_QWEN3, 151936, 1024, 28, 16, 8, 128, 3072, 128)));
+  CHECK(q06.per_layer == (2048LL + 2 * 1024) * 1024 + 1024LL * 2048 + 3LL * 3072 * 1024);
+  for (const FullLayout* f : {&l3, &q7, &gl, &q3, &q06}) {
     // the regions tile [0, n_train) exactly once
     std::vector<std::pair<int64_t, int64_t>> r = f->regions;
     std::sort(r.begin(), r.end());

@@ -104,6 +104,16 @@ template <typename AT> int gelu_fwd(hipStream_t st, const AT* x, AT* y, long n);
 template <typename AT> int gelu_bwd(hipStream_t st, const AT* dy, const AT* x, AT* dx, long n);
 template <typename AT> int embed_pos_fwd(hipStream_t st, const int* ids, const int* pos, const AT* E, const AT* P, AT* out, int T, int d, int vocab, int npos);
 template <typename AT> int rope_apply(hipStream_t st, AT* qkv, const int* pos, const float* cosT, const float* sinT, int T, int nheads_rot, int dh, long ld, int backward);
+// head_norm.hip -- Qwen3 per-head q/k RMSNorm, in place on the first (H + Hkv) 128 columns of qkv / dqkv [T, ld]: the H query heads take wq [128], the Hkv key
+// heads wk [128]; v is not touched. rstd fp32 [T, H + Hkv]. stash (forward: optional, backward: required) = the raw rows [T, H + Hkv, 128] the backward re-forms
+// x_hat from. pos != nullptr: the half-split rotation of rope_apply in the same pass (forward: norm, round, rotate; backward: un-rotate, round, norm backward),
+// bit-identical to the two passes. dwq != nullptr (with dwk and ws = HEAD_NORM_WS_FLOATS floats): dwq[j] += sum_{t, h < H} dy x_hat, dwk[j] += the key heads' sum
+// (per-workgroup partial sums + an ordered finish, no atomics)
+#define HEAD_NORM_WS_FLOATS (1024 * 256)
+template <typename AT> int head_norm_fwd(hipStream_t st, AT* qkv, long ld, const AT* wq, const AT* wk, float* rstd, AT* stash, int T, int H, int Hkv, float eps,
+                                         const int* pos, const float* cosT, const float* sinT);
+template <typename AT> int head_norm_bwd(hipStream_t st, AT* dqkv, long ld, const AT* wq, const AT* wk, const float* rstd, const AT* stash, int T, int H, int Hkv,
+                                         const int* pos, const float* cosT, const float* sinT, float* dwq, float* dwk, float* ws);
 // gu = [gate F | up F]
 template <typename AT> int swiglu_fwd(hipStream_t st, const AT* gu, AT* act, int T, int F);
 template <typename AT> int swiglu_bwd(hipStream_t st, const AT* dact, const AT* gu, AT* dgu, int T, int F);

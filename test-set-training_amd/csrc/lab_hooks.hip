@@ -345,6 +345,23 @@ int tst_k_rmsnorm_bwd_f32(const void* dy, const void* x, const float* rstd, cons
 int tst_k_rope_f32(void* qkv, const int32_t* pos, const float* cosT, const float* sinT, int T, int nheads_rot, int dh, int64_t ld, int backward) {
   return rope_apply<float>(nullptr, (float*)qkv, pos, cosT, sinT, T, nheads_rot, dh, ld, backward);
 }
+// Qwen3 per-head q/k RMSNorm (head_norm.hip)
+int tst_k_head_norm_fwd(void* qkv, int64_t ld, const void* wq, const void* wk, float* rstd, void* stash, int T, int H, int Hkv, float eps, const int32_t* pos,
+                        const float* cosT, const float* sinT) {
+  return head_norm_fwd<bf16_t>(nullptr, (bf16_t*)qkv, (long)ld, (const bf16_t*)wq, (const bf16_t*)wk, rstd, (bf16_t*)stash, T, H, Hkv, eps, pos, cosT, sinT);
+}
+int tst_k_head_norm_bwd(void* dqkv, int64_t ld, const void* wq, const void* wk, const float* rstd, const void* stash, int T, int H, int Hkv, const int32_t* pos,
+                        const float* cosT, const float* sinT, float* dwq, float* dwk, float* ws) {
+  return head_norm_bwd<bf16_t>(nullptr, (bf16_t*)dqkv, (long)ld, (const bf16_t*)wq, (const bf16_t*)wk, rstd, (const bf16_t*)stash, T, H, Hkv, pos, cosT, sinT, dwq, dwk, ws);
+}
+int tst_k_head_norm_fwd_f32(void* qkv, int64_t ld, const void* wq, const void* wk, float* rstd, void* stash, int T, int H, int Hkv, float eps, const int32_t* pos,
+                            const float* cosT, const float* sinT) {
+  return head_norm_fwd<float>(nullptr, (float*)qkv, (long)ld, (const float*)wq, (const float*)wk, rstd, (float*)stash, T, H, Hkv, eps, pos, cosT, sinT);
+}
+int tst_k_head_norm_bwd_f32(void* dqkv, int64_t ld, const void* wq, const void* wk, const float* rstd, const void* stash, int T, int H, int Hkv, const int32_t* pos,
+                            const float* cosT, const float* sinT, float* dwq, float* dwk, float* ws) {
+  return head_norm_bwd<float>(nullptr, (float*)dqkv, (long)ld, (const float*)wq, (const float*)wk, rstd, (const float*)stash, T, H, Hkv, pos, cosT, sinT, dwq, dwk, ws);
+}
 int tst_k_swiglu_fwd_f32(const void* gu, void* act, int T, int F) { return swiglu_fwd<float>(nullptr, (const float*)gu, (float*)act, T, F); }
 int tst_k_swiglu_bwd_f32(const void* dact, const void* gu, void* dgu, int T, int F) {
   return swiglu_bwd<float>(nullptr, (const float*)dact, (const float*)gu, (float*)dgu, T, F);

@@ -20,6 +20,12 @@ MODEL_SHAPES = {
     # BASELINE.json config 3's base (q/k/v bias; modeling_qwen2.py:189-191)
     "qwen2.5-7b": dict(vocab_size=152064, hidden_size=3584, num_layers=28, num_heads=28, num_kv_heads=4, head_dim=128, intermediate_size=18944,
                        rope_theta=1000000.0, rms_norm_eps=1e-6, qkv_bias=True),
+    # Qwen3 (dense): no q/k/v bias, RMSNorm over head_dim on every q and k head (modeling_qwen3.py:237-238, 252-253); head_dim is 128 at every size,
+    # so num_heads * head_dim != hidden_size at the small ones
+    "qwen3-8b": dict(vocab_size=151936, hidden_size=4096, num_layers=36, num_heads=32, num_kv_heads=8, head_dim=128, intermediate_size=12288,
+                     rope_theta=1000000.0, rms_norm_eps=1e-6, qk_norm=True),
+    "qwen3-0.6b": dict(vocab_size=151936, hidden_size=1024, num_layers=28, num_heads=16, num_kv_heads=8, head_dim=128, intermediate_size=3072,
+                       rope_theta=1000000.0, rms_norm_eps=1e-6, qk_norm=True),
     # BASELINE.json config 1's base (configuration_gpt2.py:83-103)
     "gpt2-small": dict(arch="gpt2", vocab_size=50257, hidden_size=768, num_layers=12, num_heads=12, num_kv_heads=12, head_dim=64,
                        intermediate_size=3072, max_position=1024, layer_norm_eps=1e-5),
@@ -38,7 +44,7 @@ def build_parser():
         p.add_argument("--model", default="tiny", choices=sorted(MODEL_SHAPES))
         p.add_argument("--weights-seed", type=int, default=0, help="random-init base weights (no pretrained assets offline)")
         p.add_argument("--model-dir", default=None, help="local HuggingFace checkpoint directory (config.json + model.safetensors[.index.json]; "
-                       "Llama / Qwen2 / GPT-2): shapes and weights come from it instead of --model / --weights-seed (tst/io.py)")
+                       "Llama / Qwen2 / Qwen3 / GPT-2): shapes and weights come from it instead of --model / --weights-seed (tst/io.py)")
         p.add_argument("--data", default="synthetic-vsi", help="synthetic-vsi, or with --data-file the name recorded in the outputs")
         p.add_argument("--data-file", default=None, help="QA JSONL {id, question, options (optional), answer}: the benchmark's text-only records; "
                        "needs --tokenizer (tst/io.py: load_qa_jsonl)")

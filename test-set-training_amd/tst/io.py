@@ -60,20 +60,30 @@ def checkpoint_files(model_dir):
 
 
 def cfg_from_hf(hf):
-    """HF config.json -> the cfg dict of tst.lib.Context (LlamaConfig / Qwen2Config / GPT2Config field names)."""
+    """HF config.json -> the cfg dict of tst.lib.Context (LlamaConfig / Qwen2Config / Qwen3Config / GPT2Config field names)."""
     mt = hf.get("model_type", "llama")
     if mt == "gpt2":
         d, H = hf["n_embd"], hf["n_head"]
         return dict(arch="gpt2", vocab_size=hf["vocab_size"], hidden_size=d, num_layers=hf["n_layer"], num_heads=H, num_kv_heads=H, head_dim=d // H,
                     intermediate_size=hf.get("n_inner") or 4 * d, max_position=hf["n_positions"], layer_norm_eps=hf.get("layer_norm_epsilon", 1e-5))
-    if mt not in ("llama", "qwen2"):
-        raise ValueError(f"unsupported model_type {mt!r} (llama, qwen2, gpt2)")
+    if mt not in ("llama", "qwen2", "qwen3"):
+        raise ValueError(f"unsupported model_type {mt!r} (llama, qwen2, qwen3, gpt2)")
+    if mt == "qwen3":
+        # dense Qwen3 with full attention in every layer and no projection bias is what the engine runs (include/tst_hip.h TST_ARCH_QWEN3)
+        if hf.get("use_sliding_window"):
+            raise ValueError("qwen3: use_sliding_window = true is not supported (sliding-window attention layers are not built)")
+        if "sliding_attention" in (hf.get("layer_types") or ()):
+            raise ValueError("qwen3: layer_types contains 'sliding_attention' (sliding-window attention layers are not built)")
+        if hf.get("attention_bias"):
+            raise ValueError("qwen3: attention_bias = true is not supported (q/k/v/o bias together with the q/k head norm is not built)")
     H = hf["num_attention_heads"]
     cfg = dict(vocab_size=hf["vocab_size"], hidden_size=hf["hidden_size"], num_layers=hf["num_hidden_layers"], num_heads=H,
                num_kv_heads=hf.get("num_key_value_heads", H), head_dim=hf.get("head_dim") or hf["hidden_size"] // H,
                intermediate_size=hf["intermediate_size"], rope_theta=float(hf.get("rope_theta", 10000.0)), rms_norm_eps=float(hf.get("rms_norm_eps", 1e-6)))
     if mt == "qwen2":
         cfg["qkv_bias"] = True
+    if mt == "qwen3":
+        cfg["qk_norm"] = True   # head_dim comes from the config (above): Qwen3 sizes have num_heads * head_dim != hidden_size
     # transformers >= 5 writes "rope_parameters" (which also carries rope_theta), older checkpoints "rope_scaling" + a top-level "rope_theta"
     rs = hf.get("rope_parameters") or hf.get("rope_scaling")
     if rs:

@@ -15,7 +15,7 @@ LAB_PATH = os.path.join(_LIB_DIR, "libtst_hip_lab.so")   # + test hooks and expe
 HOST_PATH = os.path.join(_HERE, "libtst_host.so")        # CPU-only: the engine's host arithmetic (csrc/host_logic.h) behind include/tst_host.h
 
 TST_OK = 0
-ARCH_LLAMA, ARCH_QWEN2, ARCH_GPT2 = 0, 1, 2  # cfg["qkv_bias"] selects the Qwen2 family, cfg["arch"] == "gpt2" the GPT-2 family
+ARCH_LLAMA, ARCH_QWEN2, ARCH_GPT2, ARCH_QWEN3 = 0, 1, 2, 3  # cfg["qkv_bias"] selects the Qwen2 family, cfg["qk_norm"] Qwen3, cfg["arch"] == "gpt2" the GPT-2 family
 TRAIN_LORA, TRAIN_FULL = 0, 1
 LORA_BITS = {"q_proj": 1, "k_proj": 2, "v_proj": 4, "o_proj": 8, "gate_proj": 16, "up_proj": 32, "down_proj": 64,
              # GPT-2 family: the four Conv1D modules
@@ -23,6 +23,7 @@ LORA_BITS = {"q_proj": 1, "k_proj": 2, "v_proj": 4, "o_proj": 8, "gate_proj": 16
 CONV1D_SUFFIXES = ("attn.c_attn.weight", "attn.c_proj.weight", "mlp.c_fc.weight", "mlp.c_proj.weight")
 LORA_ALL = 127
 DTYPE_F32, DTYPE_BF16 = 0, 1
+HEAD_NORM_WS_FLOATS = 1024 * 256   # TST_HEAD_NORM_WS_FLOATS (include/tst_hip_lab.h): scratch of the head-norm weight-gradient hooks
 PRECISION_BF16, PRECISION_STRICT = 0, 1
 
 
@@ -160,6 +161,8 @@ LAB_SIGNATURES = {
     "tst_k_rmsnorm_rank_fwd": (C.c_int, [_P, _P, _P, _P, _I, _I, _F, _P, _L, _P, _I, _F, _I, _I, _P]),
     "tst_k_rmsnorm_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I]),
     "tst_k_rope": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _L, _I]),
+    "tst_k_head_norm_fwd": (C.c_int, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
+    "tst_k_head_norm_bwd": (C.c_int, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "tst_k_swiglu_fwd": (C.c_int, [_P, _P, _I, _I]),
     "tst_k_swiglu_bwd": (C.c_int, [_P, _P, _P, _I, _I]),
     "tst_k_swiglu_rank_fwd": (C.c_int, [_P, _P, _I, _I, _P, _L, _P, _I, C.c_float, _I, _I, _P]),
@@ -186,6 +189,8 @@ LAB_SIGNATURES = {
     "tst_k_rmsnorm_fwd_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _F]),
     "tst_k_rmsnorm_bwd_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I]),
     "tst_k_rope_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _L, _I]),
+    "tst_k_head_norm_fwd_f32": (C.c_int, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P]),
+    "tst_k_head_norm_bwd_f32": (C.c_int, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "tst_k_swiglu_fwd_f32": (C.c_int, [_P, _P, _I, _I]),
     "tst_k_swiglu_bwd_f32": (C.c_int, [_P, _P, _P, _I, _I]),
 }
@@ -435,7 +440,10 @@ def make_model_cfg(cfg, max_tokens=2048, max_seqs=16, max_labelled=64, max_posit
         if tuple(lora_targets) == ("q_proj", "k_proj", "v_proj", "o_proj", "gate_proj", "up_proj", "down_proj"):
             lora_targets = ("attn.c_attn", "attn.c_proj", "mlp.c_fc", "mlp.c_proj")
     else:
-        arch, theta, eps_n = (ARCH_QWEN2 if cfg.get("qkv_bias") else ARCH_LLAMA), cfg["rope_theta"], cfg["rms_norm_eps"]
+        if cfg.get("qk_norm") and cfg.get("qkv_bias"):
+            raise ValueError("qk_norm with qkv_bias (HF Qwen3Config.attention_bias = True) is not built")
+        arch = ARCH_QWEN3 if cfg.get("qk_norm") else (ARCH_QWEN2 if cfg.get("qkv_bias") else ARCH_LLAMA)
+        theta, eps_n = cfg["rope_theta"], cfg["rms_norm_eps"]
     mask = 0
     for t in lora_targets:
         mask |= LORA_BITS[t]

@@ -7,6 +7,7 @@ imports those libraries, runs them on the deterministic inputs of tests/golden_i
 It never travels to the GPU box as a dependency: tests read the .npz files.
 
     python tools/make_golden.py            # rewrites tests/golden/*.npz
+    python tools/make_golden.py qwen3      # one family only (here: the Qwen3 fixtures, tests/qwen3_inputs.py)
 """
 import os
 import sys
@@ -24,6 +25,18 @@ torch.set_num_threads(8)
 
 
 def hf_model(cfg, weights, dtype=torch.float32):
+    if cfg.get("qk_norm"):   # Qwen3: per-head q/k RMSNorm (modeling_qwen3.py:237-238, 252-253); head_dim is its own config field
+        from transformers import Qwen3Config, Qwen3ForCausalLM
+        hc = Qwen3Config(vocab_size=cfg["vocab_size"], hidden_size=cfg["hidden_size"], intermediate_size=cfg["intermediate_size"],
+                         num_hidden_layers=cfg["num_layers"], num_attention_heads=cfg["num_heads"], num_key_value_heads=cfg["num_kv_heads"],
+                         head_dim=cfg["head_dim"], rope_theta=cfg["rope_theta"], rms_norm_eps=cfg["rms_norm_eps"], tie_word_embeddings=False,
+                         attention_bias=False, max_position_embeddings=512, use_sliding_window=False)
+        assert all(t == "full_attention" for t in hc.layer_types)
+        hc._attn_implementation = "eager"
+        m = Qwen3ForCausalLM(hc)
+        missing, unexpected = m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in weights.items()}, strict=False)
+        assert not unexpected and all("rotary" in k or "inv_freq" in k for k in missing), (missing, unexpected)
+        return m.to(dtype).train()
     if cfg.get("qkv_bias"):
         from transformers import Qwen2Config, Qwen2ForCausalLM
         hc = Qwen2Config(vocab_size=cfg["vocab_size"], hidden_size=cfg["hidden_size"], intermediate_size=cfg["intermediate_size"],
@@ -82,8 +95,9 @@ def inject_lora(m, lora, r, alpha):
     return params
 
 
-def run_llama(cfg, tag, lengths, n_answer):
-    w = GI.make_weights(cfg)
+def run_llama(cfg, tag, lengths, n_answer, make_weights=GI.make_weights, split_params=False):
+    """split_params: the adapter snapshots p1/ and p3/ go to files of their own (lora_<tag>_p1.npz, lora_<tag>_p3.npz) -- the same keys, every file under 1 MiB"""
+    w = make_weights(cfg)
     ids, labels, cu = GI.make_batch(cfg, lengths, n_answer)
     pid, plab, mask = GI.pad_batch(ids, labels, cu)
     m = hf_model(cfg, w)
@@ -137,6 +151,9 @@ def run_llama(cfg, tag, lengths, n_answer):
     with torch.no_grad():
         lg = m(input_ids=torch.from_numpy(pid), attention_mask=torch.from_numpy(mask)).logits.numpy()
     res["logits_after"] = np.concatenate([lg[b, : cu[b + 1] - cu[b]] for b in range(len(cu) - 1)]).astype(np.float32)
+    if split_params:
+        for pre in ("p1/", "p3/"):
+            np.savez_compressed(os.path.join(OUT, f"lora_{tag}_{pre[:-1]}.npz"), **{k: res.pop(k) for k in [k for k in res if k.startswith(pre)]})
     np.savez_compressed(os.path.join(OUT, f"lora_{tag}.npz"), **res)
     print(f"lora_{tag}: losses {losses} gnorms {gnorms}")
 
@@ -357,12 +374,12 @@ def _score_quantities(logits_rows, targets):
     return logp.astype(np.float32), correct, logits_rows[:, list(GI.STRICT_OPT_IDS)].astype(np.float32)
 
 
-def run_strict(cfg, tag):
+def run_strict(cfg, tag, strict_weights=GI.strict_weights):
     """fp32 end to end, non-bf16-representable weights: base logits, 20-step LoRA and full-fine-tune trajectories (clip 1.0,
     AdamW wd 0.01 with HF's two parameter groups, linear LR decay) over two alternating micro-batches, and the s(x) ingredients of
     the trained models on a 32-sample held-out set."""
     gpt2 = cfg.get("arch") == "gpt2"
-    w = GI.strict_weights(cfg)
+    w = strict_weights(cfg)
     batches = GI.strict_train_batches(cfg)
     hid, hlab, hcu = GI.strict_heldout(cfg)
     build = (lambda: hf_gpt2(cfg, w)) if gpt2 else (lambda: hf_model(cfg, w))
@@ -568,6 +585,10 @@ if __name__ == "__main__":
     if "strict" in which:
         for tag, cfg in (("tiny", GI.TINY_CFG), ("tiny2", GI.TINY2_CFG), ("qwen", GI.QWEN_CFG), ("gpt2", GI.GPT2_CFG)):
             run_strict(cfg, tag)
+    if "qwen3" in which:   # the Qwen3 family's fixtures only (llama_qwen3.npz, lora_qwen3[_p1|_p3].npz, strict_qwen3.npz): not part of the default set, so a plain run
+        import qwen3_inputs as Q3   # rewrites exactly the files it always wrote
+        run_llama(Q3.QWEN3_CFG, "qwen3", Q3.LENGTHS, Q3.N_ANSWER, make_weights=Q3.make_weights, split_params=True)
+        run_strict(Q3.QWEN3_CFG, "qwen3", strict_weights=Q3.strict_weights)
     if "accum" in which:
         for tag, cfg in (("tiny", GI.TINY_CFG), ("tiny2", GI.TINY2_CFG), ("gpt2", GI.GPT2_CFG)):
             run_accum(cfg, tag)
