@@ -338,6 +338,29 @@ int tst_score_fetch(tst_ctx* ctx, float* logp_out, int32_t* correct_out, float* 
 /* fp32 logits of selected packed token rows: logits_out[n_rows, vocab] */
 int tst_forward_logits(tst_ctx* ctx, const tst_batch* b, const int32_t* rows, int32_t n_rows, float* logits_out);
 
+/* ---- greedy generation ----
+ * Arg-max continuation of the packed prompts of b (labels ignored; seq_slot as for tst_score_async: every sequence is continued under its own slot's
+ * adapters) by max_new_tokens tokens each, with a per-context KV cache; available on every context that can score. tst_generate_async enqueues the prefill
+ * (one forward over the prompts, the head on the last token of each) and max_new_tokens - 1 decode steps (one token per sequence against its cached keys) and
+ * returns: the chosen token feeds the next step on the device, no host wait sits between steps. Sequences are not compacted when they finish, so a
+ * sequence's tokens do not depend on where its neighbours stop. tst_generate_fetch waits for the generation only (like tst_score_fetch) and cuts row s behind
+ * its first token that is in eos_ids: n_new_out[s] counts that token, the entries behind it are -1 in tokens_out and 0 in logp_out; without a hit
+ * n_new_out[s] = max_new_tokens. logp_out[s, j] = log softmax(logits)[token]. One generation may be pending per context.
+ * The cache (all layers, activation dtype, (max_tokens + max_seqs * max_new_tokens) rows of 2 * num_kv_heads * head_dim elements per layer; row of (sequence s,
+ * position p) = cu_seqlens[s] + s * max_new_tokens + p) is allocated by the first tst_generate_async of a context -- the second device allocation outside
+ * tst_create / tst_fork, counted in tst_device_bytes -- and re-allocated, behind a stream synchronisation, when a later call asks for more new tokens. Forks
+ * own theirs; a context that never generates allocates nothing.
+ * TST_EINVAL before anything is allocated or launched (the batch's own checks, e.g. a host id outside the vocabulary, included): max_new_tokens outside 1 .. TST_GEN_MAX_NEW, n_seqs > max_labelled (the head runs on n_seqs rows), a prompt with
+ * length + max_new_tokens > max_position, an eos id outside the vocabulary, n_eos > 16. tst_generate_fetch without a pending generation: TST_ESTATE.
+ * TST_BATCH_DEVICE_IDS prompts are accepted (the device-side id check applies). A generation reads the weights and adapters only: trainables, gradients,
+ * optimizer state, an open accumulation window and a pending scoring pass are left as they are. */
+#define TST_GEN_MAX_NEW 256
+int tst_generate_async(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, const int32_t* eos_ids, int32_t n_eos);
+int tst_generate_fetch(tst_ctx* ctx, int32_t* tokens_out /* [n_seqs, max_new_tokens] */, float* logp_out /* [n_seqs, max_new_tokens] */,
+                       int32_t* n_new_out /* [n_seqs] */);
+int tst_generate(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, const int32_t* eos_ids, int32_t n_eos, int32_t* tokens_out, float* logp_out,
+                 int32_t* n_new_out);
+
 /* ---- measurement hooks (bench.py): HIP events on the ctx stream around the dominant kernel class ---- */
 /* on: bit 0 = bracket every dense contraction launch with HIP events on its stream; bit 1 = also bracket the HBM-bound kernel classes
  * (variant ids 101 AdamW, 102 SwiGLU, 103 RMSNorm / LayerNorm, 104 attention); 0 = off */

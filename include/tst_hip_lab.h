@@ -103,6 +103,14 @@ int tst_k_attn_fwd_rope(const void* qkv, int64_t ld, const int32_t* cu, int n_se
 int tst_k_attn_bwd_rope(const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dO, int64_t lddo, const float* lse, float* delta,
                         const int32_t* cu, int n_seqs, int max_len, void* dqkv, int T, int H, int Hkv, int dh, float scale, const float* cosT,
                         const float* sinT);
+/* greedy generation kernels (csrc/decode.hip). meta = device int32 {n_seqs, max_new, cu[0 .. n_seqs], len[0 .. n_seqs)}; the cache row of (sequence s,
+ * position p) is cu[s] + s * max_new + p; kcache / vcache are [cap_rows, Hkv * dh].
+ * kv_append: the k | v columns qkv[t, k_off .. k_off + 2 Hkv dh) of the T rows go to cache row rows[t] (device int32 [T]), bit-exact.
+ * attn_decode: out[s, ldo] = attention of the ONE query token q[s, ldq] (H heads, rotated) over the cached keys 0 .. len[s] + step - 1 of sequence s;
+ * H / Hkv <= 8, dh 64 or 128. Rows of the cache outside a sequence's keys are never read. */
+int tst_k_kv_append(const void* qkv, int64_t ld, int k_off, const int32_t* rows, void* kcache, void* vcache, int T, int Hkv, int dh, int64_t cap_rows);
+int tst_k_attn_decode(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* meta, int n_seqs, int step, void* out, int64_t ldo, int H,
+                      int Hkv, int dh, float scale, int64_t cap_rows);
 int tst_k_adamw(float* p, const float* g, float* m, float* v, int64_t n, float max_norm, float lr, float beta1, float beta2, float eps, float wd,
                 int step, float* norm_coef_out /* device [2] */, float* partial_ws /* device [256] */);
 int tst_k_tr_probe(void* out_u16_64x8, int d0);
@@ -133,6 +141,9 @@ int tst_k_head_norm_fwd_f32(void* qkv, int64_t ld, const void* wq, const void* w
                             const float* cosT, const float* sinT);
 int tst_k_head_norm_bwd_f32(void* dqkv, int64_t ld, const void* wq, const void* wk, const float* rstd, const void* stash, int T, int H, int Hkv, const int32_t* pos,
                             const float* cosT, const float* sinT, float* dwq, float* dwk, float* ws);
+int tst_k_kv_append_f32(const void* qkv, int64_t ld, int k_off, const int32_t* rows, void* kcache, void* vcache, int T, int Hkv, int dh, int64_t cap_rows);
+int tst_k_attn_decode_f32(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* meta, int n_seqs, int step, void* out, int64_t ldo,
+                          int H, int Hkv, int dh, float scale, int64_t cap_rows);
 int tst_k_swiglu_fwd_f32(const void* gu, void* act, int T, int F);
 int tst_k_swiglu_bwd_f32(const void* dact, const void* gu, void* dgu, int T, int F);
 

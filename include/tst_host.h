@@ -37,6 +37,16 @@ int64_t tst_host_stage_ints(const tst_model_cfg* cfg);
 int tst_host_plan_batch(const tst_model_cfg* cfg, const tst_batch* b, int need_labels, int trim_last, const int32_t* rows, int n_rows, int32_t* stage,
                         int32_t* out_ints, int32_t* row_seq_out, char* err_out, int err_cap);
 
+/* tsthost::plan_generate (greedy generation, include/tst_hip.h tst_generate_async): validation and the KV-cache row map of one generation, on host
+ * buffers. out_ints[4 + 8] = {S, T, cache rows this generation uses, cache rows the context allocates for max_new, slot_s_end[8]}; meta_out [3 + 2 S]
+ * (S | max_new | cu[0 .. S] | len[0 .. S)), last_rows_out [S], prefill_rows_out [T], decode_rows_out [(max_new - 1) S] may each be NULL; err_out / err_cap
+ * receive the message of a refusal. Returns TST_OK or TST_EINVAL. */
+int tst_host_plan_generate(const tst_model_cfg* cfg, const tst_batch* b, int max_new, const int32_t* eos_ids, int n_eos, int64_t* out_ints, int32_t* meta_out,
+                           int32_t* last_rows_out, int32_t* prefill_rows_out, int32_t* decode_rows_out, char* err_out, int err_cap);
+/* the fetch side of a generation: rows of tokens / logp [n_seqs, max_new] are cut behind their first token that is in eos_ids (tokens -1, logp 0 behind it;
+ * n_new_out[s] counts the eos token), in place */
+int tst_host_cut_at_eos(int32_t* tokens, float* logp, int32_t* n_new_out, int n_seqs, int max_new, const int32_t* eos_ids, int n_eos);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

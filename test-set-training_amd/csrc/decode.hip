@@ -1,0 +1,249 @@
+// Greedy generation (tst_generate_async): the three kernels a decode step adds to the model graph of forward().
+//
+//   kv_append    copies the k and v columns of qkv [T, ld] -- behind the head norm and RoPE, i.e. as attention reads them -- into one layer's cache
+//                kcache / vcache [rows, Hkv dh] at given row indices. One 16-byte vector per lane, nothing else.
+//   attn_decode  ONE query token per sequence against that sequence's cached keys 0 .. n-1. HBM / L2-bound streaming: K and V are read exactly once.
+//                One workgroup per (sequence, kv head); the G = H / Hkv <= 8 query heads that share the kv head sit in registers. A cache row of dh elements
+//                is dh / 8 lanes x 8 elements (the lane shape of head_norm.hip: 16 lanes per 128-wide row, one 16-byte load per lane in bf16, two in fp32), so
+//                the 256 threads hold 16 (dh 128) or 32 (dh 64) "row groups"; row group r takes the keys r, r + 16, ... . The row dot product ends in DPP
+//                inside the row group. Every row group keeps a running max, sum and accumulator in fp32 (online softmax, P never rounded: there is no MFMA
+//                to feed); the row groups of a wave are merged by lane exchanges, the four waves once through LDS, in a fixed order: bit-reproducible.
+//                No atomics. Cache rows >= n of a sequence are never read.
+//   next_token   turns the {lse, logit[target], argmax, max} rows logit_rows leaves in `stats` into the step's outputs and the next step's inputs, on the
+//                device: tok[s, j] = argmax, logp[s, j] = max - lse, d_ids[s] = argmax, d_pos[s] = len[s] + j, lab_idx[s] = s.
+//
+// The generation's geometry travels in one small device array `meta` (host_logic.h plan_generate writes it):
+//   meta[0] = n_seqs S, meta[1] = max_new, meta[2 .. 2 + S] = cu_seqlens of the prompts, meta[3 + S .. 3 + 2 S) = their lengths.
+// Cache row of (sequence s, position p) = cu[s] + s max_new + p: the packed prompts with room for max_new tokens behind each.
+#include "kernels.h"
+
+// the merges below rely on both partner lanes forming the same two products and one sum: no contraction the compiler may apply to one side only; every fused
+// multiply-add is written out
+#pragma clang fp contract(off)
+
+namespace {
+
+#define CHECK_LAUNCH() (hipGetLastError() == hipSuccess ? TST_OK : TST_EHIP)
+
+template <int CTRL> __device__ __forceinline__ float dpp_mov(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+// sum over the LPR (8 or 16) lanes of a row group, the same bits in every lane: quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror
+template <int LPR> __device__ __forceinline__ float rowgroup_sum(float v) {
+  v += dpp_mov<0xB1>(v);
+  v += dpp_mov<0x4E>(v);
+  v += dpp_mov<0x141>(v);
+  if constexpr (LPR == 16) v += dpp_mov<0x140>(v);
+  return v;
+}
+
+// bf16 path: v_exp_f32 of x log2(e), as the probabilities of attn.hip; fp32 strict path: the library expf, as attn_f32.hip
+template <typename AT> __device__ __forceinline__ float exp_of(float x) {
+  if constexpr (sizeof(AT) == 2) return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
+  else return expf(x);
+}
+
+// The partial results (row groups of a wave, then the four waves) are merged in MT: fp32 on the bf16 path; fp64 on the fp32 strict path, where the merges'
+// roundings would otherwise be the largest error of the kernel -- a sequence whose softmax sits on ONE key has |out| ~ |v| of that key, and each of the six
+// merges and the normalisation rounds at that magnitude (measured against fp64 attention: 7.6e-7 with fp32 merges, 2.8e-7 with fp64 merges, 4.1e-7 the causal
+// fp32 kernel's last rows; tests/test_decode_kernels_gpu.py). A few dozen operations per lane, once per workgroup.
+template <typename AT> struct MergeT { typedef float type; };
+template <> struct MergeT<float> { typedef double type; };
+__device__ __forceinline__ float merge_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
+__device__ __forceinline__ double merge_exp(double x) { return exp(x); }
+
+template <typename AT>
+__global__ __launch_bounds__(256) void kv_append_kernel(const AT* __restrict__ qkv, long ld, int k_off, int wkv, const int* __restrict__ rows,
+                                                        AT* __restrict__ kcache, AT* __restrict__ vcache, int T, long cap_rows) {
+  constexpr int EPV = 16 / (int)sizeof(AT);   // elements per 16-byte vector
+  const int vpr = 2 * wkv / EPV;              // vectors per token: k then v
+  const long total = (long)T * vpr;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int t = (int)(i / vpr), c = (int)(i - (long)t * vpr);
+    const int is_v = c >= (vpr >> 1);
+    const int col = (c - is_v * (vpr >> 1)) * EPV;
+    const long row = rows[t];
+    if (row < 0 || row >= cap_rows) continue;   // (plan_generate keeps every row inside the cache: never taken)
+    const uint4 v = *(const uint4*)(qkv + (long)t * ld + k_off + is_v * wkv + col);
+    *(uint4*)((is_v ? vcache : kcache) + row * wkv + col) = v;
+  }
+}
+
+template <typename AT, int DH, int GP>
+__global__ __launch_bounds__(256) void attn_decode_kernel(const AT* __restrict__ q, long ldq, const AT* __restrict__ kcache, const AT* __restrict__ vcache,
+                                                          const int* __restrict__ meta, int step, AT* __restrict__ out, long ldo, int G, int Hkv, float scale,
+                                                          long cap_rows) {
+  constexpr int LPR = DH / 8;     // lanes per cache row
+  constexpr int NG = 256 / LPR;   // row groups per workgroup
+  typedef typename MergeT<AT>::type MT;
+  __shared__ MT red[4][GP][LPR * 8 + 2];
+  const int s = blockIdx.x, kvh = blockIdx.y;
+  const int S = meta[0], max_new = meta[1];
+  const int n = meta[3 + S + s] + step;                        // keys of this sequence, the new token's included
+  const long row0 = (long)meta[2 + s] + (long)s * max_new;     // cache row of its key 0
+  if (n <= 0 || row0 < 0 || row0 + n > cap_rows) return;       // (plan_generate keeps every sequence inside the cache: never taken)
+  const int tid = threadIdx.x, sub = tid % LPR, grp = tid / LPR;
+  const int wkv = Hkv * DH;
+  float qf[GP][8], acc[GP][8], m[GP], l[GP];
+#pragma unroll
+  for (int g = 0; g < GP; ++g) {
+    m[g] = -INFINITY;
+    l[g] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { acc[g][i] = 0.f; qf[g][i] = 0.f; }
+    if (g < G) ld8(q + (long)s * ldq + (long)(kvh * G + g) * DH + sub * 8, qf[g]);
+  }
+  const AT* kp = kcache + row0 * wkv + (long)kvh * DH + sub * 8;
+  const AT* vp = vcache + row0 * wkv + (long)kvh * DH + sub * 8;
+  auto one_key = [&](const float* kf, const float* vf) {
+#pragma unroll
+    for (int g = 0; g < GP; ++g) {
+      if (g < G) {
+        float d = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) d = __builtin_fmaf(qf[g][i], kf[i], d);
+        const float sc = rowgroup_sum<LPR>(d) * scale;
+        const float mn = fmaxf(m[g], sc);
+        const float corr = exp_of<AT>(m[g] - mn);   // exactly 1 while the maximum stands (0 for the first key: m = -inf)
+        const float p = exp_of<AT>(sc - mn);
+        l[g] = __builtin_fmaf(l[g], corr, p);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[g][i] = __builtin_fmaf(p, vf[i], acc[g][i] * corr);   // (acc * 1 is exact: one rounding per key while the maximum stands)
+        m[g] = mn;
+      }
+    }
+  };
+  // two keys per trip: the loads of both are in flight before the first is used
+  for (int j = grp; j < n; j += 2 * NG) {
+    float k0[8], v0[8], k1[8], v1[8];
+    const bool two = j + NG < n;
+    ld8(kp + (long)j * wkv, k0);
+    ld8(vp + (long)j * wkv, v0);
+    if (two) {
+      ld8(kp + (long)(j + NG) * wkv, k1);
+      ld8(vp + (long)(j + NG) * wkv, v1);
+    }
+    one_key(k0, v0);
+    if (two) one_key(k1, v1);
+  }
+  // merge the row groups of a wave (lanes LPR, 2 LPR, .. 32 apart): both partners add the same two products, so every lane ends with the same bits
+  MT am[GP], al[GP], aa[GP][8];
+#pragma unroll
+  for (int g = 0; g < GP; ++g) {
+    am[g] = (MT)m[g];
+    al[g] = (MT)l[g];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) aa[g][i] = (MT)acc[g][i];
+  }
+  const MT NEG_INF = (MT)(-INFINITY);
+#pragma unroll
+  for (int o = LPR; o < 64; o <<= 1) {
+#pragma unroll
+    for (int g = 0; g < GP; ++g) {
+      if (g < G) {
+        const MT mo = __shfl_xor(am[g], o, 64), lo = __shfl_xor(al[g], o, 64);
+        const MT M = am[g] > mo ? am[g] : mo;
+        const MT wa = am[g] == NEG_INF ? (MT)0 : merge_exp(am[g] - M), wb = mo == NEG_INF ? (MT)0 : merge_exp(mo - M);
+        al[g] = al[g] * wa + lo * wb;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) aa[g][i] = aa[g][i] * wa + __shfl_xor(aa[g][i], o, 64) * wb;
+        am[g] = M;
+      }
+    }
+  }
+  // the four waves, once through LDS, merged in wave order
+  const int wave = tid >> 6, lane = tid & 63;
+  if (lane < LPR) {
+#pragma unroll
+    for (int g = 0; g < GP; ++g) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) red[wave][g][sub * 8 + i] = aa[g][i];
+      if (sub == 0) { red[wave][g][LPR * 8] = am[g]; red[wave][g][LPR * 8 + 1] = al[g]; }
+    }
+  }
+  __syncthreads();
+  if (tid < G * LPR) {
+    const int g = tid / LPR;   // (sub = tid % LPR as above)
+    MT M = NEG_INF;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) M = red[w][g][LPR * 8] > M ? red[w][g][LPR * 8] : M;
+    MT L = 0, o8[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o8[i] = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+      const MT mw = red[w][g][LPR * 8];
+      const MT ww = mw == NEG_INF ? (MT)0 : merge_exp(mw - M);
+      L += red[w][g][LPR * 8 + 1] * ww;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) o8[i] += red[w][g][sub * 8 + i] * ww;
+    }
+    float of[8];   // n >= 1: at least one key carries weight exp(0) = 1, so L >= 1
+#pragma unroll
+    for (int i = 0; i < 8; ++i) of[i] = (float)(o8[i] / L);
+    st8(out + (long)s * ldo + (long)(kvh * G + g) * DH + sub * 8, of);
+  }
+}
+
+__global__ __launch_bounds__(256) void next_token_kernel(const float* __restrict__ stats, const int* __restrict__ meta, int j, int* __restrict__ tok,
+                                                         float* __restrict__ logp, int* __restrict__ d_ids, int* __restrict__ d_pos, int* __restrict__ lab_idx) {
+  const int S = meta[0], max_new = meta[1];
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= S || j < 0 || j >= max_new) return;
+  const int am = __float_as_int(stats[s * 4 + 2]);
+  tok[(long)s * max_new + j] = am;
+  logp[(long)s * max_new + j] = stats[s * 4 + 3] - stats[s * 4 + 0];
+  d_ids[s] = am;
+  d_pos[s] = meta[3 + S + s] + j;   // position of the token just chosen
+  lab_idx[s] = s;                   // the head reads every row of a decode step
+}
+
+}  // namespace
+
+template <typename AT>
+int kv_append(hipStream_t st, const AT* qkv, long ld, int k_off, const int* rows, AT* kcache, AT* vcache, int T, int Hkv, int dh, long cap_rows) {
+  if (T <= 0) return TST_OK;
+  constexpr int EPV = 16 / (int)sizeof(AT);
+  if (!qkv || !rows || !kcache || !vcache || Hkv < 1 || (dh != 64 && dh != 128) || (ld % EPV) || (k_off % EPV) || k_off < 0 || ld < (long)k_off + 2L * Hkv * dh ||
+      cap_rows <= 0)
+    return TST_EINVAL;
+  const int wkv = Hkv * dh;
+  const long want = ((long)T * (2 * wkv / EPV) + 255) / 256;
+  hipLaunchKernelGGL(kv_append_kernel<AT>, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, st, qkv, ld, k_off, wkv, rows, kcache, vcache, T, cap_rows);
+  return CHECK_LAUNCH();
+}
+
+template <typename AT>
+int attn_decode(hipStream_t st, const AT* q, long ldq, const AT* kcache, const AT* vcache, const int* meta, int n_seqs, int step, AT* out, long ldo, int H, int Hkv,
+                int dh, float scale, long cap_rows) {
+  if (n_seqs <= 0) return TST_OK;
+  if (!q || !kcache || !vcache || !meta || !out || Hkv < 1 || H < Hkv || H % Hkv || H / Hkv > 8 || (dh != 64 && dh != 128) || (ldq & 7) || (ldo & 7) ||
+      ldq < (long)H * dh || ldo < (long)H * dh || step < 0 || cap_rows <= 0 || Hkv > 65535)
+    return TST_EINVAL;
+  const int G = H / Hkv;
+  const dim3 grid((unsigned)n_seqs, (unsigned)Hkv);
+#define AD_LAUNCH(DH, GP) \
+  hipLaunchKernelGGL((attn_decode_kernel<AT, DH, GP>), grid, dim3(256), 0, st, q, ldq, kcache, vcache, meta, step, out, ldo, G, Hkv, scale, cap_rows)
+#define AD_DH(GP) do { if (dh == 128) AD_LAUNCH(128, GP); else AD_LAUNCH(64, GP); } while (0)
+  if (G == 1) AD_DH(1);
+  else if (G == 2) AD_DH(2);
+  else if (G <= 4) AD_DH(4);
+  else AD_DH(8);
+#undef AD_DH
+#undef AD_LAUNCH
+  return CHECK_LAUNCH();
+}
+
+int next_token(hipStream_t st, const float* stats, const int* meta, int n_seqs, int j, int* tok, float* logp, int* d_ids, int* d_pos, int* lab_idx) {
+  if (n_seqs <= 0) return TST_OK;
+  if (!stats || !meta || !tok || !logp || !d_ids || !d_pos || !lab_idx || j < 0) return TST_EINVAL;
+  hipLaunchKernelGGL(next_token_kernel, dim3((unsigned)((n_seqs + 255) / 256)), dim3(256), 0, st, stats, meta, j, tok, logp, d_ids, d_pos, lab_idx);
+  return CHECK_LAUNCH();
+}
+
+#define INSTANTIATE(AT)                                                                                                           \
+  template int kv_append<AT>(hipStream_t, const AT*, long, int, const int*, AT*, AT*, int, int, int, long);                      \
+  template int attn_decode<AT>(hipStream_t, const AT*, long, const AT*, const AT*, const int*, int, int, AT*, long, int, int, int, \
+                               float, long);
+INSTANTIATE(bf16_t)
+INSTANTIATE(float)

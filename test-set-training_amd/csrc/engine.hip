@@ -97,6 +97,16 @@ struct DevPool {
     bytes += n;
     return p;
   }
+  // one allocation back (the KV cache of a generation that grows): the caller has synchronised every stream that may still touch it
+  void free_one(void* p, int64_t n) {
+    for (size_t i = 0; i < ptrs.size(); ++i)
+      if (ptrs[i] == p) {
+        (void)hipFree(p);
+        ptrs.erase(ptrs.begin() + (long)i);
+        bytes -= n <= 0 ? 16 : n;
+        return;
+      }
+  }
   void release() {
     for (void* p : ptrs) (void)hipFree(p);
     ptrs.clear();
@@ -262,6 +272,22 @@ struct tst_ctx {
   int score_R = -1, score_nopt = 0;
   hipEvent_t score_evt = nullptr;  // recorded behind the result copies of tst_score_async: tst_score_fetch waits for it, not for the stream
   std::vector<int> score_tgt, score_row_seq;
+  // Greedy generation (tst_generate_async; kernels in decode.hip, row map in host_logic.h plan_generate). Allocated by the first generation of the context,
+  // for gen_cap_new new tokens per sequence; re-allocated behind a stream sync when a later call asks for more. gen_kv = K then V of layer 0, layer 1, ...:
+  // [gen_rows, Hkv dh] each in the activation dtype. gen_dev = meta | prefill_rows [Tmax] | decode_rows; gen_tok / gen_logp = the steps' outputs [S, max_new].
+  // gen_mode: 0 = forward() is the graph every other entry point runs; 1 = a generation's prefill (RoPE as its own pass, k | v of every layer appended to the
+  // cache); 2 = a decode step (one row per sequence, positions from d_pos, attn_decode against the cache).
+  void* gen_kv = nullptr;
+  int64_t gen_kv_bytes = 0, gen_dev_bytes = 0, gen_out_bytes = 0;
+  long gen_rows = 0;
+  int gen_cap_new = 0;
+  int *gen_dev = nullptr, *gen_tok = nullptr;
+  float* gen_logp = nullptr;
+  int* h_gen = nullptr;         // pinned: staging image of gen_dev | tokens [Smax, cap_new] | logp [Smax, cap_new] of the pending generation
+  hipEvent_t gen_evt = nullptr; // recorded behind the result copies: tst_generate_fetch waits for it, not for the stream
+  int gen_S = -1, gen_new = 0;  // pending generation (-1: none)
+  int gen_mode = 0, gen_step = 0;
+  std::vector<int> gen_eos;
   float* d_loss = nullptr;
   int cur_T = 0, cur_S = 0, cur_R = 0, cur_maxlen = 0, cur_items = 0;
   double cur_sumsq_len = 0;   // sum over the batch's sequences of length^2 (attention work)
@@ -942,7 +968,8 @@ int forward(CtxT<AT>* ctx, bool stash) {
     CTX_RC(linear_fwd<AT>(ctx, A.xn1, d, W.Wqkv, ctx->dqkv, W.g_qkv, A.us_qkv, nullptr, A.qkv, T, W.bqkv, u_qkv));
     // RoPE: inside the attention kernels where they can (bf16 path, sequences <= 128 tokens: q and k then stay UN-rotated in the stash and
     // the backward kernel rotates dq / dk back itself), else as a pass of its own over q and k
-    const bool rope_in = !ctx->gpt2 && rope_fused(ctx);
+    // (a generation keeps the rotation a pass of its own: the cache takes k as attention reads it, and kv_append stays a copy)
+    const bool rope_in = !ctx->gpt2 && !ctx->gen_mode && rope_fused(ctx);
     if (ctx->qk_norm) {
       // Qwen3: head norm in place on q|k, and the rotation in the same traversal whenever RoPE is a pass of its own (q|k read and written once, not twice)
       const int slot = prof_begin(ctx, st, ctx->prof_hbm);
@@ -951,7 +978,21 @@ int forward(CtxT<AT>* ctx, bool stash) {
       prof_end(ctx, st, slot, PROF_NORM, 1, (stash ? 3.0 : 2.0) * T * (ctx->dq + ctx->dkv) * sizeof(AT));
     } else
     if (!ctx->gpt2 && !rope_in) CTX_RC(rope_apply<AT>(st, A.qkv, ctx->d_pos, ctx->cosT, ctx->sinT, T, ctx->H + ctx->Hkv, ctx->dh, ctx->dqkv, 0));
-    {
+    if (ctx->gen_mode) {
+      // generation: this layer's k | v rows join the cache here -- behind the head norm and RoPE, before the activation slot is reused by the next layer
+      const long wkv = (long)ctx->Hkv * ctx->dh;
+      AT* kc = (AT*)ctx->gen_kv + (long)l * 2 * ctx->gen_rows * wkv;
+      AT* vc = kc + ctx->gen_rows * wkv;
+      const int S = ctx->cur_S;
+      const int* rows = ctx->gen_dev + (3 + 2 * ctx->Smax) + (ctx->gen_mode == 1 ? 0L : ctx->Tmax + (long)(ctx->gen_step - 1) * S);
+      CTX_RC(kv_append<AT>(st, A.qkv, ctx->dqkv, ctx->dq, rows, kc, vc, T, ctx->Hkv, ctx->dh, ctx->gen_rows));
+      if (ctx->gen_mode == 2) {
+        const int slot = prof_begin(ctx, st, ctx->prof_hbm);
+        CTX_RC(attn_decode<AT>(st, A.qkv, ctx->dqkv, kc, vc, ctx->gen_dev, S, ctx->gen_step, A.attn, ctx->dattn, ctx->H, ctx->Hkv, ctx->dh, scale, ctx->gen_rows));
+        prof_end(ctx, st, slot, PROF_ATTN, 1, 4.0 * ctx->cur_sumsq_len * ctx->H * ctx->dh);   // q . K^T + P . V over the cached keys (cur_sumsq_len = their count)
+      }
+    }
+    if (ctx->gen_mode != 2) {
       const int slot = prof_begin(ctx, st, ctx->prof_hbm);
       if (whatif() & 2) {
       } else if constexpr (sizeof(AT) == 2)
@@ -2433,6 +2474,111 @@ int score_async_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* option_id
   return TST_OK;
 }
 
+// ---- greedy generation: prefill + max_new - 1 decode steps, all enqueued at once (include/tst_hip.h tst_generate_async)
+int gen_reserve(tst_ctx* ctx, int max_new) {
+  if (ctx->gen_kv && max_new <= ctx->gen_cap_new) return TST_OK;
+  const tsthost::BatchLimits lim = {ctx->Tmax, ctx->Smax, ctx->Rmax, ctx->V, ctx->cfg.max_position, ctx->ns};
+  if (ctx->gen_kv) {   // a larger max_new: nothing of the old buffers may be in flight
+    CTX_RC(ctx_sync(ctx));
+    ctx->pool.free_one(ctx->gen_kv, ctx->gen_kv_bytes);
+    ctx->pool.free_one(ctx->gen_dev, ctx->gen_dev_bytes);
+    ctx->pool.free_one(ctx->gen_tok, ctx->gen_out_bytes);
+    if (ctx->h_gen) (void)hipHostFree(ctx->h_gen);
+    ctx->gen_kv = nullptr; ctx->gen_dev = nullptr; ctx->gen_tok = nullptr; ctx->gen_logp = nullptr; ctx->h_gen = nullptr;
+    ctx->gen_cap_new = 0; ctx->gen_S = -1;
+  }
+  const long rows = tsthost::gen_cache_rows(lim, max_new);
+  const size_t esz = ctx->strict ? 4 : 2;
+  ctx->gen_kv_bytes = (int64_t)ctx->L * 2 * rows * ctx->Hkv * ctx->dh * (int64_t)esz;
+  ctx->gen_dev_bytes = (int64_t)tsthost::gen_dev_ints(lim, max_new) * 4;
+  ctx->gen_out_bytes = (int64_t)ctx->Smax * max_new * 8;
+  ctx->gen_kv = ctx->pool.alloc(ctx->gen_kv_bytes);
+  ctx->gen_dev = (int*)ctx->pool.alloc(ctx->gen_dev_bytes);
+  ctx->gen_tok = (int*)ctx->pool.alloc(ctx->gen_out_bytes);
+  if (!ctx->gen_kv || !ctx->gen_dev || !ctx->gen_tok) {
+    if (ctx->gen_kv) ctx->pool.free_one(ctx->gen_kv, ctx->gen_kv_bytes);
+    if (ctx->gen_dev) ctx->pool.free_one(ctx->gen_dev, ctx->gen_dev_bytes);
+    if (ctx->gen_tok) ctx->pool.free_one(ctx->gen_tok, ctx->gen_out_bytes);
+    ctx->gen_kv = nullptr; ctx->gen_dev = nullptr; ctx->gen_tok = nullptr;
+    return fail(ctx, TST_ENOMEM, "hipMalloc failed: KV cache of the generation");
+  }
+  ctx->gen_logp = (float*)(ctx->gen_tok + (size_t)ctx->Smax * max_new);
+  CTX_HIP(hipStreamSynchronize(nullptr));   // the pool zero-fills on the null stream: it must not land behind this generation's first cache writes
+  CTX_HIP(hipHostMalloc((void**)&ctx->h_gen, (size_t)(ctx->gen_dev_bytes + ctx->gen_out_bytes), hipHostMallocDefault));
+  if (!ctx->gen_evt) CTX_HIP(hipEventCreateWithFlags(&ctx->gen_evt, hipEventDisableTiming));
+  CTX_HIP(hipEventRecord(ctx->gen_evt, ctx->stream));
+  ctx->gen_rows = rows;
+  ctx->gen_cap_new = max_new;
+  return TST_OK;
+}
+
+template <typename AT>
+int generate_async_impl(CtxT<AT>* ctx, const tst_batch* b, int32_t max_new, const int32_t* eos_ids, int32_t n_eos) {
+  if (!b) return TST_EINVAL;
+  if (!ctx->finalized) return fail(ctx, TST_ESTATE, "weights not finalised");
+  ctx->err.clear();
+  // what a generation adds to a batch's checks is refused here, before an allocation or a launch (plan_generate walks cu_seqlens and seq_slot itself to build
+  // the row map, so it repeats plan_batch's checks of those two)
+  const tsthost::BatchLimits lim = {ctx->Tmax, ctx->Smax, ctx->Rmax, ctx->V, ctx->cfg.max_position, ctx->ns};
+  tsthost::GenPlan plan;
+  {
+    std::string perr;
+    if (tsthost::plan_generate(b, lim, max_new, eos_ids, n_eos, plan, perr) != TST_OK) return fail(ctx, TST_EINVAL, perr);
+  }
+  if (ctx->H % ctx->Hkv || ctx->H / ctx->Hkv > 8 || (ctx->dh != 64 && ctx->dh != 128))
+    return fail(ctx, TST_EINVAL, "generation needs head_dim 64 or 128 and at most 8 query heads per kv head");
+  hipStream_t st = ctx->stream;
+  const int S = plan.S;
+  // the prompts as a batch whose head rows are the last token of each: upload_batch refuses what plan_batch finds (ids outside the vocabulary) on the host,
+  // before its own copies -- and before the cache is allocated or grown, so a refused generation leaves the context's memory as it was
+  CTX_RC(upload_batch(ctx, b, false, plan.last_rows.data(), S));
+  ctx->gen_S = -1;
+  CTX_RC(gen_reserve(ctx, max_new));
+  CTX_RC(ctx_event_sync(ctx, ctx->gen_evt));   // the staging image may still feed the previous generation's copy
+  {
+    int* h = ctx->h_gen;
+    const size_t o_pre = (size_t)3 + 2 * (size_t)ctx->Smax, o_dec = o_pre + (size_t)ctx->Tmax;
+    memcpy(h, plan.meta.data(), plan.meta.size() * sizeof(int));
+    memcpy(h + o_pre, plan.prefill_rows.data(), plan.prefill_rows.size() * sizeof(int));
+    if (!plan.decode_rows.empty()) memcpy(h + o_dec, plan.decode_rows.data(), plan.decode_rows.size() * sizeof(int));
+    CTX_HIP(hipMemcpyAsync(ctx->gen_dev, h, (o_dec + plan.decode_rows.size()) * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  auto step_tail = [&](int j) -> int {
+    CTX_RC(head_forward(ctx, false));
+    CTX_RC(logit_rows<AT>(st, ctx->logits, ctx->Vp, ctx->d_targets, S, ctx->V, ctx->stats, nullptr, 0, 0.f, nullptr, 0, ctx->optl));
+    return next_token(st, ctx->stats, ctx->gen_dev, S, j, ctx->gen_tok, ctx->gen_logp, ctx->d_ids, ctx->d_pos, ctx->d_lab_idx);
+  };
+  ctx->gen_mode = 1; ctx->gen_step = 0;
+  int rc = forward(ctx, false);
+  ctx->gen_mode = 0;
+  CTX_RC(rc);
+  CTX_RC(step_tail(0));
+  if (max_new > 1) {
+    // decode steps: the same forward() over one row per sequence. "Tokens" are sequences now: the slot boundaries are sequence counts, the head reads every row
+    ctx->cur_T = ctx->cur_S = ctx->cur_R = S;
+    ctx->cur_maxlen = 1;
+    for (int q = 0; q < TST_MAX_STACK; ++q) ctx->slot_ends.t_end[q] = ctx->row_ends.t_end[q] = plan.slot_s_end[q];
+    double keys = (double)plan.T;
+    for (int j = 1; j < max_new && rc == TST_OK; ++j) {
+      keys += S;
+      ctx->cur_sumsq_len = keys;
+      ctx->gen_mode = 2; ctx->gen_step = j;
+      rc = forward(ctx, false);
+      ctx->gen_mode = 0;
+      if (rc == TST_OK) rc = step_tail(j);
+    }
+    CTX_RC(rc);
+  }
+  float* h_out = (float*)(ctx->h_gen + ctx->gen_dev_bytes / 4);
+  CTX_HIP(hipMemcpyAsync(h_out, ctx->gen_tok, (size_t)S * max_new * 4, hipMemcpyDeviceToHost, st));
+  CTX_HIP(hipMemcpyAsync(h_out + (size_t)ctx->Smax * ctx->gen_cap_new, ctx->gen_logp, (size_t)S * max_new * 4, hipMemcpyDeviceToHost, st));
+  CTX_HIP(hipEventRecord(ctx->gen_evt, st));
+  ctx->gen_eos.assign(eos_ids, eos_ids + n_eos);
+  ctx->gen_S = S;
+  ctx->gen_new = max_new;
+  return TST_OK;
+}
+
 template <typename AT>
 int forward_logits_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* rows, int32_t n_rows, float* logits_out) {
   if (!b || !rows || !logits_out || n_rows <= 0) return TST_EINVAL;
@@ -2603,6 +2749,8 @@ int tst_destroy(tst_ctx* ctx) {
   }
   if (ctx->h_metrics) (void)hipHostFree(ctx->h_metrics);
   if (ctx->h_score) (void)hipHostFree(ctx->h_score);
+  if (ctx->h_gen) (void)hipHostFree(ctx->h_gen);
+  if (ctx->gen_evt) (void)hipEventDestroy(ctx->gen_evt);
   if (ctx->score_evt) (void)hipEventDestroy(ctx->score_evt);
   if (ctx->h_opt_ids) (void)hipHostFree(ctx->h_opt_ids);
   if (ctx->h_idflag) (void)hipHostFree(ctx->h_idflag);
@@ -2963,6 +3111,36 @@ int tst_score(tst_ctx* ctx, const tst_batch* b, const int32_t* option_ids, int32
   int rc = tst_score_async(ctx, b, option_ids, n_opt);
   if (rc != TST_OK) return rc;
   return tst_score_fetch(ctx, logp_out, correct_out, opt_logit_out, row_seq_out, n_rows_out);
+}
+
+int tst_generate_async(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, const int32_t* eos_ids, int32_t n_eos) {
+  if (!ctx || !b) return TST_EINVAL;
+  return typed(ctx, [&](auto* c) { return generate_async_impl(c, b, max_new_tokens, eos_ids, n_eos); });
+}
+
+int tst_generate_fetch(tst_ctx* ctx, int32_t* tokens_out, float* logp_out, int32_t* n_new_out) {
+  if (!ctx) return TST_EINVAL;
+  if (ctx->gen_S < 0) return fail(ctx, TST_ESTATE, "tst_generate_fetch without a pending tst_generate_async");
+  CTX_RC(ctx_event_sync(ctx, ctx->gen_evt));   // work enqueued after the generation keeps running
+  const int S = ctx->gen_S, n = ctx->gen_new;
+  ctx->gen_S = -1;
+  const int32_t* h_tok = (const int32_t*)(ctx->h_gen + ctx->gen_dev_bytes / 4);
+  const float* h_lp = (const float*)h_tok + (size_t)ctx->Smax * ctx->gen_cap_new;
+  std::vector<int32_t> tok(h_tok, h_tok + (size_t)S * n);
+  std::vector<float> lp(h_lp, h_lp + (size_t)S * n);
+  std::vector<int32_t> nn((size_t)S);
+  tsthost::cut_at_eos(tok.data(), lp.data(), nn.data(), S, n, ctx->gen_eos.data(), (int)ctx->gen_eos.size());
+  if (tokens_out) memcpy(tokens_out, tok.data(), tok.size() * 4);
+  if (logp_out) memcpy(logp_out, lp.data(), lp.size() * 4);
+  if (n_new_out) memcpy(n_new_out, nn.data(), nn.size() * 4);
+  return TST_OK;
+}
+
+int tst_generate(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, const int32_t* eos_ids, int32_t n_eos, int32_t* tokens_out, float* logp_out,
+                 int32_t* n_new_out) {
+  int rc = tst_generate_async(ctx, b, max_new_tokens, eos_ids, n_eos);
+  if (rc != TST_OK) return rc;
+  return tst_generate_fetch(ctx, tokens_out, logp_out, n_new_out);
 }
 
 int tst_forward_logits(tst_ctx* ctx, const tst_batch* b, const int32_t* rows, int32_t n_rows, float* logits_out) {

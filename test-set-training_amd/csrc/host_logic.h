@@ -222,4 +222,83 @@ inline int plan_batch(const tst_batch* b, const BatchLimits& lim, bool need_labe
   return TST_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ greedy generation: validation + the cache row map
+// A generation continues the packed prompts of `b` by max_new tokens each. The KV cache of a layer is [rows, Hkv dh] with the row of (sequence s, position p)
+// = cu[s] + s max_new + p: the packed prompts with room for the new tokens behind each; it holds max_tokens + max_seqs max_new rows (gen_cache_rows).
+// plan_generate refuses what the engine cannot run BEFORE anything is launched and fills the staging image of the generation's device array:
+//   meta         [3 + 2 S]        S | max_new | cu[0 .. S] | len[0 .. S)                       (what attn_decode / next_token read, csrc/decode.hip)
+//   last_rows    [S]              packed index of every prompt's last token: the rows the prefill's head runs on
+//   prefill_rows [T]              cache row of every prompt token
+//   decode_rows  [(max_new-1) S]  cache row of the token decode step j = 1 .. max_new - 1 appends for sequence s, at [(j - 1) S + s]
+//   slot_s_end   [kMaxStack]      sequences of slots 0 .. q (a decode step's "tokens" are its sequences: these are its slot boundaries)
+// input_ids is never dereferenced (it may be a device pointer); ids and lengths 1 .. max_position are plan_batch's to check.
+constexpr int kGenMaxNew = 256;   // == TST_GEN_MAX_NEW
+constexpr int kGenMaxEos = 16;
+inline long gen_cache_rows(const BatchLimits& l, int max_new) { return (long)l.Tmax + (long)l.Smax * max_new; }
+// ints of the device array at capacity: meta | prefill_rows | decode_rows
+inline size_t gen_dev_ints(const BatchLimits& l, int max_new) { return (size_t)(3 + 2 * l.Smax) + (size_t)l.Tmax + (size_t)l.Smax * (size_t)max_new; }
+struct GenPlan {
+  int S = 0, T = 0, max_new = 0;
+  long rows_used = 0;   // rows of the cache this generation touches (<= gen_cache_rows)
+  std::vector<int> meta, last_rows, prefill_rows, decode_rows;
+  int slot_s_end[kMaxStack];
+};
+inline int plan_generate(const tst_batch* b, const BatchLimits& lim, int max_new, const int32_t* eos_ids, int n_eos, GenPlan& out, std::string& err) {
+  auto fail = [&](const char* m) { err = m; return TST_EINVAL; };
+  if (!b) return fail("null batch");
+  if (max_new < 1 || max_new > kGenMaxNew) return fail("max_new_tokens out of range (1..TST_GEN_MAX_NEW)");
+  if (n_eos < 0 || n_eos > kGenMaxEos || (n_eos > 0 && !eos_ids)) return fail("more than 16 eos ids (or a null list)");
+  for (int i = 0; i < n_eos; ++i)
+    if (eos_ids[i] < 0 || eos_ids[i] >= lim.V) return fail("eos id out of vocabulary");
+  const int T = b->n_tokens, S = b->n_seqs;
+  if (T <= 0 || S <= 0 || T > lim.Tmax || S > lim.Smax) return fail("batch exceeds max_tokens/max_seqs or is empty");
+  if (S > lim.Rmax) return fail("more sequences than max_labelled: the head runs on one row per sequence");
+  if (!b->input_ids || !b->cu_seqlens) return fail("null batch pointers");
+  if (b->cu_seqlens[0] != 0 || b->cu_seqlens[S] != T) return fail("cu_seqlens must start at 0 and end at n_tokens");
+  out.S = S; out.T = T; out.max_new = max_new;
+  out.meta.assign((size_t)3 + 2 * (size_t)S, 0);
+  out.last_rows.assign((size_t)S, 0);
+  out.prefill_rows.assign((size_t)T, 0);
+  out.decode_rows.assign((size_t)(max_new - 1) * (size_t)S, 0);
+  out.meta[0] = S; out.meta[1] = max_new;
+  int cur_slot = 0;
+  for (int s = 0; s < S; ++s) {
+    const int s0 = b->cu_seqlens[s], s1 = b->cu_seqlens[s + 1];
+    if (s0 < 0 || s1 > T || s1 < s0) return fail("cu_seqlens must be non-decreasing and within n_tokens");
+    const int len = s1 - s0;
+    if (len <= 0) return fail("sequence length out of range (1..max_position)");
+    if ((long)len + max_new > lim.max_position) return fail("prompt length + max_new_tokens exceeds max_position");
+    if (b->seq_slot) {
+      const int sl = b->seq_slot[s];
+      if (sl < cur_slot || sl >= lim.ns) return fail("seq_slot must be non-decreasing and < n_stack");
+      for (; cur_slot < sl; ++cur_slot) out.slot_s_end[cur_slot] = s;
+    }
+    out.meta[(size_t)2 + s] = s0;
+    out.meta[(size_t)3 + S + s] = len;
+    out.last_rows[(size_t)s] = s1 - 1;
+    const int row0 = s0 + s * max_new;
+    for (int p = 0; p < len; ++p) out.prefill_rows[(size_t)s0 + p] = row0 + p;
+    for (int j = 1; j < max_new; ++j) out.decode_rows[(size_t)(j - 1) * S + s] = row0 + len + j - 1;
+  }
+  out.meta[(size_t)2 + S] = T;
+  for (; cur_slot < kMaxStack; ++cur_slot) out.slot_s_end[cur_slot] = S;
+  out.rows_used = (long)T + (long)S * max_new;
+  return TST_OK;
+}
+// the fetch side: row s of tokens / logp [S, max_new] is cut behind its first token that is in eos_ids -- n_new[s] counts that token, the entries behind
+// it become -1 / 0; without a hit n_new[s] = max_new. In place.
+inline void cut_at_eos(int32_t* tokens, float* logp, int32_t* n_new, int S, int max_new, const int32_t* eos_ids, int n_eos) {
+  for (int s = 0; s < S; ++s) {
+    int n = max_new;
+    for (int j = 0; j < max_new && n == max_new; ++j)
+      for (int e = 0; e < n_eos; ++e)
+        if (tokens[(size_t)s * max_new + j] == eos_ids[e]) { n = j + 1; break; }
+    for (int j = n; j < max_new; ++j) {
+      tokens[(size_t)s * max_new + j] = -1;
+      if (logp) logp[(size_t)s * max_new + j] = 0.0f;
+    }
+    if (n_new) n_new[s] = n;
+  }
+}
+
 }  // namespace tsthost

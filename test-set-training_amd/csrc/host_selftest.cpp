@@ -207,7 +207,74 @@ static void test_zero_and_layout() {
   for (int i = 1; i < 64; ++i) CHECK(rope_inv_freq(c3, i, 128) <= rope_inv_freq(c3, i - 1, 128));
 }
 
+// plan_generate: the cache row map is injective, inside the cache, in prompt order with room behind every prompt; decode rows continue each prompt;
+// every refusal of include/tst_hip.h is refused. Random ragged prompt batches, arrays at their exact sizes.
+static void test_plan_generate() {
+  std::mt19937 rng(31u);
+  for (int it = 0; it < 300; ++it) {
+    const int ns = (it % 3 == 0) ? 1 + (int)(rng() % 4u) : 1;
+    const int S = ns + (int)(rng() % 12u), max_len = 1 + (int)(rng() % 40u), V = 50, max_new = 1 + (int)(rng() % 9u);
+    Batch x = make_batch(rng, S, max_len, V, ns, false);
+    x.b.input_ids = (const int32_t*)(uintptr_t)16;   // never dereferenced: the ids may live on the device
+    const BatchLimits lim = {x.b.n_tokens + (int)(rng() % 3u), S + (int)(rng() % 3u), S, V, max_len + max_new, ns};
+    const int32_t eos[2] = {0, V - 1};
+    GenPlan g;
+    std::string err;
+    CHECK(plan_generate(&x.b, lim, max_new, eos, 2, g, err) == TST_OK);
+    const long cap = gen_cache_rows(lim, max_new);
+    CHECK(g.S == S && g.T == x.b.n_tokens && g.rows_used <= cap && g.rows_used == (long)x.b.n_tokens + (long)S * max_new);
+    CHECK((int)g.meta.size() == 3 + 2 * S && g.meta[0] == S && g.meta[1] == max_new && (int)g.decode_rows.size() == (max_new - 1) * S);
+    CHECK(gen_dev_ints(lim, max_new) >= (size_t)(3 + 2 * lim.Smax) + (size_t)lim.Tmax + g.decode_rows.size());
+    std::vector<char> seen((size_t)cap, 0);
+    for (int s = 0; s < S; ++s) {
+      const int s0 = x.cu[(size_t)s], len = x.cu[(size_t)s + 1] - s0;
+      CHECK(g.meta[(size_t)2 + s] == s0 && g.meta[(size_t)3 + S + s] == len && g.last_rows[(size_t)s] == s0 + len - 1);
+      for (int p = 0; p < len + max_new - 1; ++p) {
+        const int row = p < len ? g.prefill_rows[(size_t)s0 + p] : g.decode_rows[(size_t)(p - len) * S + s];
+        CHECK(row == s0 + s * max_new + p && row >= 0 && row < g.rows_used);
+        if (row >= 0 && row < cap) { CHECK(!seen[(size_t)row]); seen[(size_t)row] = 1; }
+      }
+    }
+    CHECK(g.meta[(size_t)2 + S] == x.b.n_tokens);
+    for (int q = 0; q < kMaxStack; ++q) {
+      int want = 0;
+      for (int s = 0; s < S; ++s) want += (ns > 1 ? x.slot[(size_t)s] : 0) <= q;
+      CHECK(g.slot_s_end[q] == want);
+    }
+    // refusals
+    GenPlan r;
+    CHECK(plan_generate(&x.b, lim, 0, eos, 2, r, err) == TST_EINVAL && err.find("max_new_tokens") != std::string::npos);
+    CHECK(plan_generate(&x.b, lim, kGenMaxNew + 1, eos, 2, r, err) == TST_EINVAL && err.find("max_new_tokens") != std::string::npos);
+    const int32_t bad_eos[1] = {V};
+    CHECK(plan_generate(&x.b, lim, max_new, bad_eos, 1, r, err) == TST_EINVAL && err.find("eos id") != std::string::npos);
+    int32_t many[kGenMaxEos + 1] = {0};
+    CHECK(plan_generate(&x.b, lim, max_new, many, kGenMaxEos + 1, r, err) == TST_EINVAL && err.find("16 eos") != std::string::npos);
+    CHECK(plan_generate(&x.b, lim, max_new, many, kGenMaxEos, r, err) == TST_OK);
+    BatchLimits few = lim; few.Rmax = S - 1;
+    CHECK(plan_generate(&x.b, few, max_new, nullptr, 0, r, err) == TST_EINVAL && err.find("max_labelled") != std::string::npos);
+    int longest = 0;
+    for (int s = 0; s < S; ++s) longest = std::max(longest, x.cu[(size_t)s + 1] - x.cu[(size_t)s]);
+    BatchLimits shortpos = lim; shortpos.max_position = longest + max_new - 1;
+    CHECK(plan_generate(&x.b, shortpos, max_new, nullptr, 0, r, err) == TST_EINVAL && err.find("max_position") != std::string::npos);
+    shortpos.max_position = longest + max_new;
+    CHECK(plan_generate(&x.b, shortpos, max_new, nullptr, 0, r, err) == TST_OK);
+    CHECK(plan_generate(nullptr, lim, max_new, nullptr, 0, r, err) == TST_EINVAL);
+  }
+  // the fetch side: rows cut behind the first eos token
+  int32_t tok[3 * 4] = {5, 6, 7, 8, 9, 2, 9, 2, 1, 1, 1, 3};
+  float lp[3 * 4];
+  for (float& v : lp) v = -1.0f;
+  int32_t n_new[3];
+  const int32_t eos[2] = {2, 3};
+  cut_at_eos(tok, lp, n_new, 3, 4, eos, 2);
+  CHECK(n_new[0] == 4 && n_new[1] == 2 && n_new[2] == 4);
+  CHECK(tok[3] == 8 && tok[4] == 9 && tok[5] == 2 && tok[6] == -1 && tok[7] == -1 && lp[5] == -1.0f && lp[6] == 0.0f && lp[7] == 0.0f && tok[11] == 3 && lp[11] == -1.0f);
+  cut_at_eos(tok, nullptr, n_new, 3, 4, nullptr, 0);
+  CHECK(n_new[1] == 4);
+}
+
 int main() {
+  test_plan_generate();
   test_plan_batch();
   test_zero_and_layout();
   if (g_fail) { fprintf(stderr, "%d checks failed\n", g_fail); return 1; }

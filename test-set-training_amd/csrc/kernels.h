@@ -172,6 +172,16 @@ int attn_fwd(hipStream_t st, const float* qkv, long ld, const int* cu, int n_seq
 int attn_bwd(hipStream_t st, const float* qkv, long ld, const float* out, long ldo, const float* dO, long lddo, const float* lse, float* delta,
              const int* cu, int n_seqs, int max_len, float* dqkv, int T, int H, int Hkv, int dh, float scale);
 int tr_probe(hipStream_t st, unsigned short* out_dev, int d0);
+// decode.hip -- greedy generation. meta = device ints S | max_new | cu[0 .. S] | len[0 .. S) (host_logic.h plan_generate); the cache row of (sequence s,
+// position p) is cu[s] + s max_new + p; cap_rows = rows behind kcache / vcache (a row outside it is skipped, never touched).
+// kv_append: the k | v columns qkv[t, k_off .. k_off + 2 Hkv dh) -> kcache / vcache [cap_rows, Hkv dh] row rows[t], 16-byte vectors, bit-exact.
+template <typename AT> int kv_append(hipStream_t st, const AT* qkv, long ld, int k_off, const int* rows, AT* kcache, AT* vcache, int T, int Hkv, int dh, long cap_rows);
+// attn_decode: out[s, h dh ..] = softmax(scale q[s, h] . K_s^T) V_s over the keys 0 .. len[s] + step - 1 of sequence s; q [n_seqs, ldq] holds the (rotated) query
+// heads, H / Hkv <= 8, dh 64 or 128. fp32 online softmax, no atomics, bit-reproducible.
+template <typename AT> int attn_decode(hipStream_t st, const AT* q, long ldq, const AT* kcache, const AT* vcache, const int* meta, int n_seqs, int step, AT* out,
+                                       long ldo, int H, int Hkv, int dh, float scale, long cap_rows);
+// next_token: from the rows logit_rows left in stats: tok[s, j] = argmax, logp[s, j] = max - lse, d_ids[s] = argmax, d_pos[s] = len[s] + j, lab_idx[s] = s
+int next_token(hipStream_t st, const float* stats, const int* meta, int n_seqs, int j, int* tok, float* logp, int* d_ids, int* d_pos, int* lab_idx);
 
 // One LoRA "module group" = adapters of linears that share an input (q,k,v | o | gate,up | down).
 template <typename AT>

@@ -362,6 +362,22 @@ int tst_k_head_norm_bwd_f32(void* dqkv, int64_t ld, const void* wq, const void* 
                             const float* cosT, const float* sinT, float* dwq, float* dwk, float* ws) {
   return head_norm_bwd<float>(nullptr, (float*)dqkv, (long)ld, (const float*)wq, (const float*)wk, rstd, (const float*)stash, T, H, Hkv, pos, cosT, sinT, dwq, dwk, ws);
 }
+int tst_k_kv_append(const void* qkv, int64_t ld, int k_off, const int32_t* rows, void* kcache, void* vcache, int T, int Hkv, int dh, int64_t cap_rows) {
+  return kv_append<bf16_t>(nullptr, (const bf16_t*)qkv, (long)ld, k_off, rows, (bf16_t*)kcache, (bf16_t*)vcache, T, Hkv, dh, (long)cap_rows);
+}
+int tst_k_kv_append_f32(const void* qkv, int64_t ld, int k_off, const int32_t* rows, void* kcache, void* vcache, int T, int Hkv, int dh, int64_t cap_rows) {
+  return kv_append<float>(nullptr, (const float*)qkv, (long)ld, k_off, rows, (float*)kcache, (float*)vcache, T, Hkv, dh, (long)cap_rows);
+}
+int tst_k_attn_decode(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* meta, int n_seqs, int step, void* out, int64_t ldo, int H,
+                      int Hkv, int dh, float scale, int64_t cap_rows) {
+  return attn_decode<bf16_t>(nullptr, (const bf16_t*)q, (long)ldq, (const bf16_t*)kcache, (const bf16_t*)vcache, meta, n_seqs, step, (bf16_t*)out, (long)ldo, H, Hkv,
+                             dh, scale, (long)cap_rows);
+}
+int tst_k_attn_decode_f32(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* meta, int n_seqs, int step, void* out, int64_t ldo,
+                          int H, int Hkv, int dh, float scale, int64_t cap_rows) {
+  return attn_decode<float>(nullptr, (const float*)q, (long)ldq, (const float*)kcache, (const float*)vcache, meta, n_seqs, step, (float*)out, (long)ldo, H, Hkv, dh,
+                            scale, (long)cap_rows);
+}
 int tst_k_swiglu_fwd_f32(const void* gu, void* act, int T, int F) { return swiglu_fwd<float>(nullptr, (const float*)gu, (float*)act, T, F); }
 int tst_k_swiglu_bwd_f32(const void* dact, const void* gu, void* dgu, int T, int F) {
   return swiglu_bwd<float>(nullptr, (const float*)dact, (const float*)gu, (float*)dgu, T, F);

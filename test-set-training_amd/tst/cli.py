@@ -86,6 +86,11 @@ def build_parser():
                        "the gradient inside the library; launch with torch.distributed.run, world size a multiple of --dp); one fold per group "
                        "at a time, no stacking. UNVERIFIED ON MULTI-GPU HARDWARE: the 2-rank exchange has only run on CPU stand-ins and with "
                        "1-rank communicators on one MI355X; a rank whose step fails aborts its communicator and exits non-zero")
+        p.add_argument("--generate", action="store_true", help="also generate every held-out sample's answer (greedy, KV cache; include/tst_hip.h "
+                       "tst_generate_async): the records gain gen (token ids), gen_correct and, with a tokenizer, gen_text. Off: the run is unchanged")
+        p.add_argument("--max-new-tokens", type=int, default=8, help="with --generate: tokens generated per sample (1..256)")
+        p.add_argument("--eos-ids", default=None, help="with --generate: comma-separated token ids that end an answer; default: eos_token_id of "
+                       "<model-dir>/generation_config.json or config.json when present, else none")
         if name == "prune":
             p.add_argument("--rounds", type=int, default=4)
             p.add_argument("--tau", type=float, default=0.5)
@@ -129,9 +134,32 @@ def apply_config(a, argv):
     return a
 
 
+def default_eos_ids(model_dir):
+    """eos_token_id (an int or a list) of <model-dir>/generation_config.json, else of config.json; () when neither names one"""
+    for name in ("generation_config.json", "config.json"):
+        path = os.path.join(model_dir, name) if model_dir else None
+        if path and os.path.exists(path):
+            with open(path) as fh:
+                e = json.load(fh).get("eos_token_id")
+            if e is not None:
+                return tuple(int(x) for x in (e if isinstance(e, (list, tuple)) else [e]))
+    return ()
+
+
+def parse_eos_ids(a):
+    """--eos-ids / the YAML key eos_ids: "2,32000", a list, or an int; unset: the checkpoint's own"""
+    e = getattr(a, "eos_ids", None)
+    if e is None or e == "":
+        return default_eos_ids(getattr(a, "model_dir", None))
+    if isinstance(e, str):
+        return tuple(int(x) for x in e.replace(",", " ").split())
+    return tuple(int(x) for x in (e if isinstance(e, (list, tuple)) else [e]))
+
+
 def _args_to_train(a):
     from .trainer import TrainArgs
-    return TrainArgs(learning_rate=a.learning_rate, num_train_epochs=a.num_train_epochs, per_device_train_batch_size=a.per_device_train_batch_size,
+    gen = dict(generate=True, max_new_tokens=int(a.max_new_tokens), eos_ids=parse_eos_ids(a)) if getattr(a, "generate", False) else {}
+    return TrainArgs(**gen, learning_rate=a.learning_rate, num_train_epochs=a.num_train_epochs, per_device_train_batch_size=a.per_device_train_batch_size,
                      warmup_steps=a.warmup_steps, weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm, seed=a.seed, lora_r=a.lora_r,
                      lora_alpha=a.lora_alpha, logging_steps=a.logging_steps, gradient_accumulation_steps=max(1, a.gradient_accumulation_steps))
 
@@ -163,10 +191,14 @@ def _make_ctx(a, targs, local_rank, rank=0, world=1, max_answer=4):
         cfg = MODEL_SHAPES[a.model]
     bs = max(targs.per_device_train_batch_size, targs.per_device_eval_batch_size)
     L = max(128, a.max_len)
+    if targs.generate:   # room for the generated tokens behind the longest prompt: RoPE table / wpe rows (max_tokens, sized from L below, grows with it)
+        L += targs.max_new_tokens
     if a.layout == "dp-stacked":   # every rank hosts ALL k folds, laid out as one GPU would lay them out alone
         F, S, nctx = fold_layout(cfg, a.train_mode, a.k, 0, 1, a.folds_per_gpu or a.k, a.stack)
     else:
         F, S, nctx = (1, 1, 1) if a.dp > 1 else fold_layout(cfg, a.train_mode, a.k, rank, world, a.folds_per_gpu, a.stack)
+    if targs.generate and cfg.get("arch") == "gpt2" and a.max_len + targs.max_new_tokens > cfg["max_position"]:
+        raise SystemExit(f"--generate: --max-len {a.max_len} + --max-new-tokens {targs.max_new_tokens} exceeds the model's {cfg['max_position']} positions")
     ctx = lib.Context(cfg, device=local_rank, max_tokens=bs * L * S, max_seqs=bs * S, max_labelled=max(4, max_answer) * bs * S,
                       max_position=min(L, cfg["max_position"]) if cfg.get("arch") == "gpt2" else L, lora_r=targs.lora_r,
                       lora_alpha=targs.lora_alpha, lora_targets=targs.lora_targets, beta1=targs.adam_beta1, beta2=targs.adam_beta2,
@@ -231,6 +263,13 @@ def main(argv=None):
             raise SystemExit("--data-file needs --tokenizer (or --model-dir with a tokenizer.json)")
         samples, opt_ids = TIO.load_qa_jsonl(a.data_file, tok, max_len=a.max_len)
         targs.option_ids = tuple(opt_ids)
+    decode = None
+    if targs.generate:
+        tok_file = a.tokenizer or (os.path.join(a.model_dir, "tokenizer.json") if a.model_dir else None)
+        if tok_file and os.path.exists(tok_file):
+            from tokenizers import Tokenizer
+            _tk = Tokenizer.from_file(tok_file)
+            decode = lambda ids: _tk.decode(list(ids))   # noqa: E731
     max_answer = max((len(x.ids) - x.n_prompt for x in samples), default=4) if samples else 4
     ctx, cfg = _make_ctx(a, targs, local_rank, rank, world, max_answer)   # a list: the root context and its resident forks
     if samples is None:
@@ -259,7 +298,7 @@ def main(argv=None):
             for c in ctx:
                 c.dp_init(c.dp_unique_id(), 1, 0)
         identity["layout"] = "dp-stacked"
-        run_diag = lambda smp, rnd: DG.diagnose_dp_stacked(ctx, smp, a.k, targs, rank, world, rnd, a.out, log=log, identity=identity)   # noqa: E731
+        run_diag = lambda smp, rnd: DG.diagnose_dp_stacked(ctx, smp, a.k, targs, rank, world, rnd, a.out, log=log, identity=identity, decode=decode)   # noqa: E731
     elif a.dp > 1:
         # the fold group's communicator: the 128-byte RCCL id travels over a gloo group (CPU); libtst_hip is loaded before torch
         # (the contexts above), so the collectives run on the ROCm runtime the kernels were built against
@@ -273,9 +312,9 @@ def main(argv=None):
         if a.dp_transport == "bf16":
             ctx[0].dp_set_transport("bf16")
         identity["dp_mode"] = a.dp_mode
-        run_diag = lambda smp, rnd: DG.diagnose_dp(ctx[0], smp, a.k, targs, rank, world, a.dp, rnd, a.out, log=log, identity=identity, mode=a.dp_mode)   # noqa: E731
+        run_diag = lambda smp, rnd: DG.diagnose_dp(ctx[0], smp, a.k, targs, rank, world, a.dp, rnd, a.out, log=log, identity=identity, mode=a.dp_mode, decode=decode)   # noqa: E731
     else:
-        run_diag = lambda smp, rnd: DG.diagnose(ctx, smp, a.k, targs, rank, world, rnd, a.out, log=log, identity=identity)               # noqa: E731
+        run_diag = lambda smp, rnd: DG.diagnose(ctx, smp, a.k, targs, rank, world, rnd, a.out, log=log, identity=identity, decode=decode)   # noqa: E731
     if a.cmd == "diagnose":
         recs, stats = run_diag(samples, 0)
         for st in stats:

@@ -5,6 +5,8 @@ collective: fold f runs on rank f % world. A finished fold writes 
 held-out sample); that file is the checkpoint/resume unit (a crashed worker's fold is simply re-run) and the C2
 "gather" of the build: rank 0 concatenates the shards. Record schema (frozen, SURVEY §7 hard part 2):
     {"id": int, "fold": int, "round": int, "s": float, "pred": int, "correct": int, "kind": "mca"|"na"}
+With TrainArgs.generate every record also carries what the text-only model answers: "gen" (the greedy continuation of the prompt, token ids without the
+eos token), "gen_correct" (it starts with the reference answer's ids) and, when the caller hands a `decode` function (the CLI: its tokenizer), "gen_text".
 """
 import json
 import os
@@ -14,8 +16,10 @@ import time
 import numpy as np
 
 from . import kfold
-from .trainer import (TrainArgs, fine_tune, fine_tune_concurrent, fine_tune_dp, fine_tune_stacked, score_heldout, score_heldout_concurrent,
-                      score_heldout_stacked)
+from .trainer import (TrainArgs, fine_tune, fine_tune_concurrent, fine_tune_dp, fine_tune_stacked, generate_heldout, generate_heldout_concurrent,
+                      generate_heldout_stacked, score_heldout, score_heldout_concurrent, score_heldout_stacked)
+
+GEN_ARGS = ("generate", "max_new_tokens", "eos_ids")   # TrainArgs fields that enter the run fingerprint only when generation is on
 
 
 def run_fingerprint(samples, k, args, extra=None):
@@ -26,6 +30,9 @@ def run_fingerprint(samples, k, args, extra=None):
     import hashlib
     h = hashlib.sha256()
     a = dataclasses.asdict(args) if dataclasses.is_dataclass(args) else dict(args)
+    if not a.get("generate"):   # a run without generation is the run it was before the option existed: its directory still resumes
+        for kk in GEN_ARGS:
+            a.pop(kk, None)
     h.update(json.dumps(dict(args={kk: (list(v) if isinstance(v, tuple) else v) for kk, v in sorted(a.items())}, k=int(k), n=len(samples),
                              extra=extra or {}), sort_keys=True).encode())
     for x in samples:
@@ -73,11 +80,24 @@ def train_health(recs):
                 grad_norm_min=float(gn.min()), grad_norm_max=float(gn.max()))
 
 
+def fold_records(held, f, rnd, s, pred, correct, gen=None, decode=None):
+    """the records of one scored held-out fold; gen = [(gen ids, gen_correct)] per sample when generation is on, decode = ids -> text"""
+    records = [dict(id=int(x.sid), fold=int(f), round=int(rnd), s=float(si), pred=int(pi), correct=int(ci), kind=x.kind)
+               for x, si, pi, ci in zip(held, s, pred, correct)]
+    if gen is not None:
+        for r, (g, gc) in zip(records, gen):
+            r["gen"] = [int(t) for t in g]
+            r["gen_correct"] = int(gc)
+            if decode is not None:
+                r["gen_text"] = decode(r["gen"])
+    return records
+
+
 def fold_path(out_dir, rnd, f):
     return os.path.join(out_dir, f"round_{rnd}", f"fold_{f}.jsonl")
 
 
-def run_fold(ctx, samples, assign, f, args: TrainArgs, rnd=0, out_dir=None, log=None):
+def run_fold(ctx, samples, assign, f, args: TrainArgs, rnd=0, out_dir=None, log=None, decode=None):
     """fine-tune on the k-1 other folds, score the held-out fold; returns the records (and writes the shard)."""
     train_idx, held_idx = kfold.fold_indices(assign, f)
     t0 = time.perf_counter()
@@ -86,17 +106,11 @@ def run_fold(ctx, samples, assign, f, args: TrainArgs, rnd=0, out_dir=None, log=
     t1 = time.perf_counter()
     held = [samples[i] for i in held_idx]
     s, pred, correct = score_heldout(ctx, held, args)
+    gen = generate_heldout(ctx, held, args) if args.generate else None
     t2 = time.perf_counter()
-    records = [dict(id=int(x.sid), fold=int(f), round=int(rnd), s=float(si), pred=int(pi), correct=int(ci), kind=x.kind)
-               for x, si, pi, ci in zip(held, s, pred, correct)]
+    records = fold_records(held, f, rnd, s, pred, correct, gen, decode)
     if out_dir:
-        path = fold_path(out_dir, rnd, f)
-        os.makedirs(os.path.dirname(path), exist_ok=True)
-        tmp = path + ".tmp"
-        with open(tmp, "w") as fh:
-            for r in records:
-                fh.write(json.dumps(r) + "\n")
-        os.replace(tmp, path)  # atomic: a shard either exists completely or not at all
+        _write_shard(out_dir, rnd, f, records)
     stats = dict(fold=f, n_train=len(train_idx), n_heldout=len(held_idx), train_s=t1 - t0, score_s=t2 - t1,
                  acc=float(np.mean(correct)) if len(correct) else 0.0, last_loss=recs_train[-1]["loss"] if recs_train else None, **train_health(recs_train))
     return records, stats
@@ -112,7 +126,7 @@ def _write_shard(out_dir, rnd, f, records):
     os.replace(tmp, path)  # atomic: a shard either exists completely or not at all
 
 
-def run_fold_group(ctxs, samples, assign, fold_ids, args: TrainArgs, rnd=0, out_dir=None, log=None):
+def run_fold_group(ctxs, samples, assign, fold_ids, args: TrainArgs, rnd=0, out_dir=None, log=None, decode=None):
     """len(fold_ids) <= len(ctxs) folds at once on one GPU (resident folds: contexts forked from one root). Same records and
     shards as run_fold; the timings in the stats are the group's wall time."""
     stacked = any(getattr(c, "n_stack", 1) > 1 for c in ctxs)
@@ -126,14 +140,14 @@ def run_fold_group(ctxs, samples, assign, fold_ids, args: TrainArgs, rnd=0, out_
     t1 = time.perf_counter()
     helds = [[samples[i] for i in he] for _, he in idx]
     scored = (score_heldout_stacked if stacked else score_heldout_concurrent)(ctxs, helds, args)
+    gens = (generate_heldout_stacked if stacked else generate_heldout_concurrent)(ctxs, helds, args) if args.generate else [None] * len(helds)
     t2 = time.perf_counter()
     if os.environ.get("TST_PHASE_LOG"):
         import sys
         print(f"[phase] fold group {list(fold_ids)}: train {t1 - t0:.3f} s, score {t2 - t1:.3f} s", file=sys.stderr)
     all_records, stats = [], []
-    for f, (tr, he), held, (s, pred, correct), lg in zip(fold_ids, idx, helds, scored, logs):
-        records = [dict(id=int(x.sid), fold=int(f), round=int(rnd), s=float(si), pred=int(pi), correct=int(ci), kind=x.kind)
-                   for x, si, pi, ci in zip(held, s, pred, correct)]
+    for f, (tr, he), held, (s, pred, correct), gen, lg in zip(fold_ids, idx, helds, scored, gens, logs):
+        records = fold_records(held, f, rnd, s, pred, correct, gen, decode)
         if out_dir:
             _write_shard(out_dir, rnd, f, records)
         all_records += records
@@ -144,10 +158,11 @@ def run_fold_group(ctxs, samples, assign, fold_ids, args: TrainArgs, rnd=0, out_
     return all_records, stats
 
 
-def diagnose(ctx, samples, k, args: TrainArgs, rank=0, world=1, rnd=0, out_dir=None, resume=True, log=None, identity=None):
+def diagnose(ctx, samples, k, args: TrainArgs, rank=0, world=1, rnd=0, out_dir=None, resume=True, log=None, identity=None, decode=None):
     """runs this rank's folds; returns (records of this rank, per-fold stats). `ctx` is one context (folds run one after the
     other) or a list of contexts sharing one GPU (root + forks): then that many folds run at once. `identity`: what the caller knows
-    about model / weights / data (any JSON-able dict); it goes into the run fingerprint that guards resume."""
+    about model / weights / data (any JSON-able dict); it goes into the run fingerprint that guards resume. `decode` (ids -> text): with args.generate the
+    records also carry "gen_text"."""
     assign = kfold.kfold_assign(len(samples), k, True, args.seed)
     if out_dir and resume:
         check_fingerprint(out_dir, rnd, run_fingerprint(samples, k, args, identity), rank)
@@ -162,19 +177,19 @@ def diagnose(ctx, samples, k, args: TrainArgs, rank=0, world=1, rnd=0, out_dir=N
     if cap > 1:
         group = list(ctx) if isinstance(ctx, (list, tuple)) else [ctx]
         for g in range(0, len(todo), cap):
-            r, st = run_fold_group(group, samples, assign, todo[g:g + cap], args, rnd, out_dir, log)
+            r, st = run_fold_group(group, samples, assign, todo[g:g + cap], args, rnd, out_dir, log, decode)
             records += r
             stats += st
         return records, stats
     one = ctx[0] if isinstance(ctx, (list, tuple)) else ctx
     for f in todo:
-        r, st = run_fold(one, samples, assign, f, args, rnd, out_dir, log)
+        r, st = run_fold(one, samples, assign, f, args, rnd, out_dir, log, decode)
         records += r
         stats.append(st)
     return records, stats
 
 
-def diagnose_dp(ctx, samples, k, args: TrainArgs, rank, world, dp, rnd=0, out_dir=None, resume=True, log=None, identity=None, mode="shard"):
+def diagnose_dp(ctx, samples, k, args: TrainArgs, rank, world, dp, rnd=0, out_dir=None, resume=True, log=None, identity=None, mode="shard", decode=None):
     """BASELINE.json config 4: groups of `dp` ranks share a fold (tst/ddp.py; the context has joined its group's communicator,
     ddp.init_fold_group). Fold f goes to group f mod n_groups; the group's ranks fine-tune it together (fine_tune_dp), rank 0 of the
     group scores the held-out fold and writes the shard. Returns (records, stats) of the folds this rank wrote (empty on the
@@ -200,9 +215,9 @@ def diagnose_dp(ctx, samples, k, args: TrainArgs, rank, world, dp, rnd=0, out_di
             continue   # the replicas are identical: one of them scores
         held = [samples[i] for i in he]
         s, pred, correct = score_heldout(ctx, held, args)
+        gen = generate_heldout(ctx, held, args) if args.generate else None
         t2 = time.perf_counter()
-        recs = [dict(id=int(x.sid), fold=int(f), round=int(rnd), s=float(si), pred=int(pi), correct=int(ci), kind=x.kind)
-                for x, si, pi, ci in zip(held, s, pred, correct)]
+        recs = fold_records(held, f, rnd, s, pred, correct, gen, decode)
         if out_dir:
             _write_shard(out_dir, rnd, f, recs)
         records += recs
@@ -211,7 +226,7 @@ def diagnose_dp(ctx, samples, k, args: TrainArgs, rank, world, dp, rnd=0, out_di
     return records, stats
 
 
-def diagnose_dp_stacked(ctxs, samples, k, args: TrainArgs, rank, world, rnd=0, out_dir=None, resume=True, log=None, identity=None, gather=None):
+def diagnose_dp_stacked(ctxs, samples, k, args: TrainArgs, rank, world, rnd=0, out_dir=None, resume=True, log=None, identity=None, gather=None, decode=None):
     """the dp-stacked layout: EVERY rank hosts all k folds (stacked contexts, the one-GPU layout) and the ranks share every fold's
     fine-tune -- global batches of world x per_device_train_batch_size samples, each rank its own micro-batch, one gradient all-reduce
     per context and step (trainer.fine_tune_stacked(dp=...); the contexts have joined their communicators, ddp.init_stacked_groups).
@@ -248,10 +263,10 @@ def diagnose_dp_stacked(ctxs, samples, k, args: TrainArgs, rank, world, rnd=0, o
         t1 = time.perf_counter()
         helds = [[samples[i] for i in he][rank::world] for _, he in idx]      # this rank's part of every held-out fold
         scored = score_heldout_stacked(group, helds, args)
+        gens = generate_heldout_stacked(group, helds, args) if args.generate else [None] * len(helds)
         t2 = time.perf_counter()
-        for f, (tr, he), held, (s, pred, correct), lg in zip(fold_ids, idx, helds, scored, logs):
-            recs = [dict(id=int(x.sid), fold=int(f), round=int(rnd), s=float(si), pred=int(pi), correct=int(ci), kind=x.kind)
-                    for x, si, pi, ci in zip(held, s, pred, correct)]
+        for f, (tr, he), held, (s, pred, correct), gen, lg in zip(fold_ids, idx, helds, scored, gens, logs):
+            recs = fold_records(held, f, rnd, s, pred, correct, gen, decode)
             if out_dir:
                 parts = gather(recs)
                 if rank == 0:

@@ -119,6 +119,26 @@ class TstModel:
 
     forward = __call__
 
+    def generate(self, input_ids, attention_mask=None, max_new_tokens=20, eos_token_id=None, pad_token_id=None, **_unused):
+        """greedy GenerationMixin.generate for RIGHT-padded inputs (HF/generation/utils.py: do_sample False, num_beams 1): returns the HF-shaped
+        [B, S + max_new_tokens] int64 array -- every row its prompt, then its new tokens up to and including the first eos, then padding (pad_token_id,
+        default the first eos id, else 0). Unlike HF, whose decoder-only models want LEFT padding, the new tokens follow each row's own end."""
+        input_ids = _np(input_ids)
+        if input_ids.ndim != 2:
+            raise ValueError("input_ids must be [batch, seq]")
+        mask = _np(attention_mask) if attention_mask is not None else np.ones_like(input_ids)
+        ids, _, cu = D.from_padded(input_ids, mask, np.zeros_like(input_ids))
+        eos = () if eos_token_id is None else tuple(int(e) for e in (eos_token_id if isinstance(eos_token_id, (list, tuple)) else [eos_token_id]))
+        tok, _, n_new = self.ctx.generate(ids, cu, int(max_new_tokens), eos)
+        pad = int(pad_token_id) if pad_token_id is not None else (eos[0] if eos else 0)
+        B, S = input_ids.shape
+        out = np.full((B, S + int(max_new_tokens)), pad, np.int64)
+        lens = np.diff(cu)
+        for b in range(B):
+            out[b, :lens[b]] = input_ids[b, :lens[b]]
+            out[b, lens[b]:lens[b] + n_new[b]] = tok[b, :n_new[b]]
+        return out
+
     def _eval_loss(self, ids, lab, cu, num_items):
         logp, _, _, _ = self.ctx.score_rows(ids, lab, cu, ())
         n = int(num_items) if num_items is not None else len(logp)

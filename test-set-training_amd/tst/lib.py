@@ -132,6 +132,9 @@ SIGNATURES = {
     "tst_fetch_loss": (C.c_int, [_P, _P]),
     "tst_score": (C.c_int, [_P, C.POINTER(Batch), _P, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
     "tst_forward_logits": (C.c_int, [_P, C.POINTER(Batch), _P, C.c_int32, _P]),
+    "tst_generate_async": (C.c_int, [_P, C.POINTER(Batch), C.c_int32, _P, C.c_int32]),
+    "tst_generate_fetch": (C.c_int, [_P, _P, _P, _P]),
+    "tst_generate": (C.c_int, [_P, C.POINTER(Batch), C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "tst_profile_enable": (C.c_int, [_P, _I]),
     "tst_profile_read": (C.c_int, [_P, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_L), _I]),
     "tst_profile_intervals": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _L, C.POINTER(_L)]),
@@ -177,6 +180,10 @@ LAB_SIGNATURES = {
     "tst_k_attn_bwd": (C.c_int, [_P, _L, _P, _L, _P, _L, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _F]),
     "tst_k_attn_fwd_rope": (C.c_int, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _I, _F, _P, _P]),
     "tst_k_attn_bwd_rope": (C.c_int, [_P, _L, _P, _L, _P, _L, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _F, _P, _P]),
+    "tst_k_kv_append": (C.c_int, [_P, _L, _I, _P, _P, _P, _I, _I, _I, _L]),
+    "tst_k_attn_decode": (C.c_int, [_P, _L, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _F, _L]),
+    "tst_k_kv_append_f32": (C.c_int, [_P, _L, _I, _P, _P, _P, _I, _I, _I, _L]),
+    "tst_k_attn_decode_f32": (C.c_int, [_P, _L, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _F, _L]),
     "tst_k_adamw": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _I, _P, _P]),
     "tst_k_tr_probe": (C.c_int, [_P, _I]),
     "tst_k_gemm_pp_stamps": (C.c_int, [_P]),
@@ -203,6 +210,8 @@ HOST_SIGNATURES = {
     "tst_host_full_layout": (C.c_int, [_P, _P, _P, _I, _P]),
     "tst_host_stage_ints": (_L, [_P]),
     "tst_host_plan_batch": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I]),
+    "tst_host_plan_generate": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I]),
+    "tst_host_cut_at_eos": (C.c_int, [_P, _P, _P, _I, _I, _P, _I]),
 }
 
 
@@ -307,6 +316,42 @@ def host_plan_batch(mc, ids, labels, cu, seq_slot=None, need_labels=True, trim_l
     return dict(T_dev=T, S=S, R=R, maxlen=int(out[3]), slot_t_end=out[4:12].copy(), slot_r0=out[12:21].copy(), row_end=out[21:29].copy(),
                 ids=stage[:T].copy(), pos=stage[o_pos:o_pos + T].copy(), cu=stage[o_cu:o_cu + S + 1].copy(), lab_idx=stage[o_lab:o_lab + R].copy(),
                 targets=stage[o_tgt:o_tgt + R].copy(), row_seq=rseq[:R].copy())
+
+
+GEN_MAX_NEW = 256   # TST_GEN_MAX_NEW (include/tst_hip.h)
+
+
+def host_plan_generate(mc, ids, cu, max_new, eos_ids=(), seq_slot=None):
+    """tsthost::plan_generate through the CPU library: dict(S, T, rows_used, cache_rows, slot_s_end, meta, last_rows, prefill_rows, decode_rows [max_new - 1, S]);
+    raises TstError with the library's message for a refused generation"""
+    L = load_host()
+    ids = np.ascontiguousarray(ids, np.int32)
+    cu = np.ascontiguousarray(cu, np.int32)
+    sl = None if seq_slot is None else np.ascontiguousarray(seq_slot, np.int32)
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    S, T = len(cu) - 1, len(ids)
+    b = Batch(ip(ids), None, ip(cu), S, T, ip(sl), 0)
+    eos = np.ascontiguousarray(eos_ids, np.int32)
+    out, err = np.zeros(12, np.int64), C.create_string_buffer(256)
+    meta, last, pre = np.zeros(3 + 2 * max(S, 0), np.int32), np.zeros(max(S, 1), np.int32), np.zeros(max(T, 1), np.int32)
+    dec = np.zeros(max(1, (min(max(int(max_new), 1), GEN_MAX_NEW) - 1) * max(S, 0)), np.int32)
+    rc = L.tst_host_plan_generate(C.byref(mc), C.byref(b), int(max_new), _ptr(eos) if len(eos) else None, len(eos), _ptr(out), _ptr(meta), _ptr(last), _ptr(pre),
+                                  _ptr(dec), err, 256)
+    if rc != 0:
+        raise TstError(err.value.decode() or f"tst_host_plan_generate rc={rc}")
+    return dict(S=int(out[0]), T=int(out[1]), rows_used=int(out[2]), cache_rows=int(out[3]), slot_s_end=out[4:12].astype(np.int32), meta=meta, last_rows=last[:S],
+                prefill_rows=pre[:T], decode_rows=dec[:(int(max_new) - 1) * S].reshape(int(max_new) - 1, S))
+
+
+def host_cut_at_eos(tokens, logp, eos_ids):
+    """(tokens, logp, n_new) with every row cut behind its first eos token, as tst_generate_fetch does"""
+    tok = np.array(tokens, np.int32, ndmin=2)
+    lp = np.array(logp, np.float32, ndmin=2)
+    eos = np.ascontiguousarray(eos_ids, np.int32)
+    nn = np.zeros(tok.shape[0], np.int32)
+    if load_host().tst_host_cut_at_eos(_ptr(tok), _ptr(lp), _ptr(nn), tok.shape[0], tok.shape[1], _ptr(eos) if len(eos) else None, len(eos)) != 0:
+        raise TstError("tst_host_cut_at_eos: bad arguments")
+    return tok, lp, nn
 
 
 def device_count():
@@ -790,6 +835,26 @@ class Context:
     def score_rows(self, ids, labels, cu, option_ids=(), seq_slot=None):
         self.score_rows_async(ids, labels, cu, option_ids, seq_slot)
         return self.score_rows_fetch()
+
+    # ---- greedy generation (include/tst_hip.h tst_generate_async)
+    def generate_async(self, ids, cu, max_new_tokens, eos_ids=(), seq_slot=None):
+        """enqueue the greedy continuation of the packed prompts (ids, cu) by max_new_tokens tokens each; results come from generate_fetch()."""
+        b, keep = self._batch(ids, None, cu, seq_slot)
+        eos_a, _ = _i32(np.asarray(eos_ids, np.int32) if len(eos_ids) else np.zeros(1, np.int32))
+        self._check(self.lib.tst_generate_async(self.h, C.byref(b), int(max_new_tokens), _ptr(eos_a), len(eos_ids)), "tst_generate_async")
+        self._pending_gen = (len(keep[2]) - 1, int(max_new_tokens))
+
+    def generate_fetch(self):
+        """(tokens [n_seqs, max_new] int32, logp [n_seqs, max_new], n_new [n_seqs]): rows are cut behind their first eos token (-1 / 0 behind it)"""
+        n, m = getattr(self, "_pending_gen", None) or (1, 1)
+        tok, logp, n_new = np.full((n, m), -1, np.int32), np.zeros((n, m), np.float32), np.zeros(n, np.int32)
+        self._check(self.lib.tst_generate_fetch(self.h, _ptr(tok), _ptr(logp), _ptr(n_new)), "tst_generate_fetch")
+        self._pending_gen = None
+        return tok, logp, n_new
+
+    def generate(self, ids, cu, max_new_tokens, eos_ids=(), seq_slot=None):
+        self.generate_async(ids, cu, max_new_tokens, eos_ids, seq_slot)
+        return self.generate_fetch()
 
     def forward_logits(self, ids, cu, rows, seq_slot=None):
         b, keep = self._batch(ids, None, cu, seq_slot)

@@ -5,6 +5,9 @@ only names s(x), so the definition is this build's and is frozen here):
     position; s(x) = p[ground truth], prediction = argmax over the options.
   * numeric / open answer (1..4 tokens): s(x) = exp(mean_t log p(answer_t | prefix)), teacher-forced;
     correct iff every answer token is the arg-max token.
+
+With generation switched on (TrainArgs.generate) a sample also carries what the text-only model SAYS: its greedy continuation of the prompt
+(generated_answers), and gen_correct = that continuation starts with the reference answer's tokens. bias_scores does not change.
 """
 import numpy as np
 
@@ -32,3 +35,18 @@ def bias_scores(samples, logp, correct_rows, opt_logits, row_seq):
             s[i] = np.exp(np.mean(logp[rows].astype(np.float64)))
             correct[i] = int(correct_rows[rows].all())
     return s, pred, correct
+
+
+def generated_answers(samples, tokens, n_new, eos_ids=()):
+    """samples: the prompts' samples in batch order; tokens [n, max_new] / n_new [n] as returned by Context.generate (rows cut behind their first eos
+    token). Returns per sample (gen, gen_correct): gen = the generated ids without the eos token, gen_correct = 1 when the first n_answer generated
+    ids equal the reference answer ids."""
+    eos = set(int(e) for e in eos_ids)
+    out = []
+    for i, smp in enumerate(samples):
+        gen = [int(t) for t in np.asarray(tokens[i])[:int(n_new[i])]]
+        if gen and gen[-1] in eos:
+            gen = gen[:-1]
+        ans = [int(t) for t in smp.ids[smp.n_prompt:]]
+        out.append((gen, int(len(ans) > 0 and gen[:len(ans)] == ans)))
+    return out

@@ -33,6 +33,11 @@ class TrainArgs:
     logging_steps: int = 50
     gradient_accumulation_steps: int = 1   # HF training_args.py: micro-batches per optimizer update, normalised by ONE num_items_in_batch (trainer.py:1740-1758, 2141-2175)
     option_ids: tuple = D.OPTION_IDS   # token ids of the option letters (synthetic data: reserved ids; real data: from the tokenizer)
+    # greedy answer generation on the held-out fold (off by default: a run without it computes and writes exactly what it did before these fields existed,
+    # and tst.diagnose.run_fingerprint leaves them out): every record gains what the text-only model says, `gen`, and `gen_correct`
+    generate: bool = False
+    max_new_tokens: int = 8
+    eos_ids: tuple = ()
 
 
 def linear_lr(step, total, lr0, warmup=0):
@@ -191,6 +196,89 @@ def score_heldout(ctx, samples, args: TrainArgs):
         s, p, c = S.bias_scores(batch, logp, corr, optl, rseq)
         s_all.append(s); p_all.append(p); c_all.append(c)
     return np.concatenate(s_all), np.concatenate(p_all), np.concatenate(c_all)
+
+
+# ---------------------------------------------------------------------------------------------- greedy answers of the held-out fold
+def collate_prompts(samples):
+    """packed prompts (ids[:n_prompt] of every sample): ids, cu_seqlens"""
+    ids = np.concatenate([s.ids[:s.n_prompt] for s in samples]).astype(np.int32)
+    cu = np.concatenate([[0], np.cumsum([s.n_prompt for s in samples])]).astype(np.int32)
+    return ids, cu
+
+
+def generate_heldout(ctx, samples, args: TrainArgs):
+    """greedy continuation of every held-out prompt (Context.generate, batches of per_device_eval_batch_size); returns [(gen ids, gen_correct)]
+    per sample in input order (tst.score.generated_answers)."""
+    bs = args.per_device_eval_batch_size
+    out = []
+    for b in range(0, len(samples), bs):
+        batch = samples[b:b + bs]
+        ids, cu = collate_prompts(batch)
+        tok, _, n_new = ctx.generate(ids, cu, args.max_new_tokens, args.eos_ids)
+        out += S.generated_answers(batch, tok, n_new, args.eos_ids)
+    return out
+
+
+def generate_heldout_concurrent(ctxs, sample_sets, args: TrainArgs):
+    """generate_heldout for several resident folds: batch b of every fold is enqueued before batch b-1's results are read."""
+    bs = args.per_device_eval_batch_size
+    outs = [[] for _ in ctxs]
+    pending = [None] * len(ctxs)
+
+    def fetch(j):
+        if pending[j] is not None:
+            tok, _, n_new = ctxs[j].generate_fetch()
+            outs[j] += S.generated_answers(pending[j], tok, n_new, args.eos_ids)
+            pending[j] = None
+
+    nb = max((len(smp) + bs - 1) // bs for smp in sample_sets) if sample_sets else 0
+    for b in range(nb):
+        for j, (c, smp) in enumerate(zip(ctxs, sample_sets)):
+            fetch(j)
+            batch = smp[b * bs:(b + 1) * bs]
+            if batch:
+                ids, cu = collate_prompts(batch)
+                c.generate_async(ids, cu, args.max_new_tokens, args.eos_ids)
+                pending[j] = batch
+    for j in range(len(ctxs)):
+        fetch(j)
+    return outs
+
+
+def generate_heldout_stacked(ctxs, sample_sets, args: TrainArgs):
+    """generate_heldout on stacked contexts: batch b of all folds of a context is one generation, every sequence under its own slot's adapters;
+    returns [(gen ids, gen_correct)] per fold, in the order of sample_sets."""
+    where = place_folds(len(sample_sets), ctxs)
+    bs = args.per_device_eval_batch_size
+    outs = [[] for _ in sample_sets]
+    pending = [None] * len(ctxs)
+    mine = [[(sl, i) for i, (jj, sl) in enumerate(where) if jj == j] for j in range(len(ctxs))]
+
+    def fetch(j):
+        if pending[j] is not None:
+            parts = pending[j]   # [(fold position, samples)]
+            tok, _, n_new = ctxs[j].generate_fetch()
+            got = S.generated_answers([x for _, b in parts for x in b], tok, n_new, args.eos_ids)
+            o = 0
+            for i, b in parts:
+                outs[i] += got[o:o + len(b)]
+                o += len(b)
+            pending[j] = None
+
+    nb = max((len(smp) + bs - 1) // bs for smp in sample_sets) if sample_sets else 0
+    for b in range(nb):
+        for j, c in enumerate(ctxs):
+            fetch(j)
+            parts = [(sl, i, sample_sets[i][b * bs:(b + 1) * bs]) for sl, i in mine[j]]
+            parts = [(sl, i, x) for sl, i, x in parts if x]
+            if parts:
+                ids, cu = collate_prompts([x for _, _, xs in parts for x in xs])
+                seq_slot = np.concatenate([np.full(len(xs), sl, np.int32) for sl, _, xs in parts])
+                c.generate_async(ids, cu, args.max_new_tokens, args.eos_ids, seq_slot)
+                pending[j] = [(i, xs) for _, i, xs in parts]
+    for j in range(len(ctxs)):
+        fetch(j)
+    return outs
 
 
 # ---------------------------------------------------------------------------------------------- stacked folds
