@@ -11,6 +11,7 @@
 #include <math.h>
 #include <stdio.h>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <string>
@@ -123,6 +124,16 @@ struct LoraGroupT {
   int index = -1;  // position in ctx->descs
 };
 
+// one of a layer's four projections y = x . W^T, in the order the flat buffer of a full fine-tune, the optimizer and tst_init_random visit them
+enum { P_QKV = 0, P_O = 1, P_GU = 2, P_D = 3 };
+template <typename AT>
+struct ProjT {
+  AT *W = nullptr, *WT = nullptr;   // [dout, din] and its transpose for dX (nullptr: dX contracts against W itself, tst_ctx::kmajor bit 0)
+  int dout = 0, din = 0;
+  const LoraGroupT<AT>* g = nullptr;   // the module group on it (in the same LayerT)
+  int64_t numel() const { return (int64_t)dout * din; }
+};
+
 template <typename AT>
 struct LayerT {
   AT *attn_norm, *mlp_norm;
@@ -133,7 +144,7 @@ struct LayerT {
   AT* qk_raw = nullptr;        // stash [T, (H + Hkv) 128]: q|k as the projection wrote them (the head norm runs in place; its backward re-forms x_hat from this)
   float* rstd_qk = nullptr;    // [T, H + Hkv]
   AT *attn_norm_b = nullptr, *mlp_norm_b = nullptr, *bo = nullptr, *bgu = nullptr, *bd = nullptr;  // GPT-2: LayerNorm and Conv1D biases
-  AT *Wqkv, *WqkvT, *Wo, *WoT, *Wgu, *WguT, *Wd, *WdT;
+  ProjT<AT> proj[4];
   LoraGroupT<AT> g_qkv, g_o, g_gu, g_d;
   // stash
   AT *x_in, *xn1, *qkv, *attn, *hmid, *xn2, *gu, *act;
@@ -161,6 +172,7 @@ struct tst_ctx {
   bool finalized = false;
 
   int d, L, H, Hkv, dh, F, V, dq, dkv, dqkv, dattn;
+  int proj_dout[4] = {0}, proj_din[4] = {0};   // widths of a layer's four projections (P_QKV .. P_D)
   // GPT-2 family (TST_ARCH_GPT2): LayerNorm with bias, learned positions wpe, biased Conv1D linears, gelu_new MLP (one
   // fc projection of width F instead of gate|up), no RoPE, head tied to the token embedding.
   // intra-fold data parallelism: one RCCL communicator per fold group, collectives enqueued on this ctx's stream
@@ -190,7 +202,6 @@ struct tst_ctx {
   float* colred_ws = nullptr;   // full fine-tune: slice sums of the norm-weight / bias gradient reductions (two launches, no atomics: kernels.h colred_ws_floats)
   bool gn_fused = false;          // the slots describe the gradient now in tg (not after a data-parallel reduction / a caller's own)
   int last_variant = -1, last_sk = 1;   // tile family and split of the last run_gemm
-  bool dp_in_step = false;   // set by tst_train_step_dp_async around its backward: only then are the regions reduced
   int64_t dp_n_coll = 0, dp_n_elems = 0;   // collectives enqueued / fp32 elements reduced since tst_dp_init (tst_dp_stats)
   // optimizer-state sharding (cfg.zero_ranks > 1, full fine-tune): tp / tm / tv hold the elements [z_lo, z_hi) of the flat trainable vector
   // only (index i of the vector lives at tp[i - z_lo]); tg and the compute copy wb are full length, padded to n_pad = zero_ranks * z_shard
@@ -241,17 +252,15 @@ struct tst_ctx {
   SlotEnds row_ends;                     // current batch: labelled rows of slot s end at row_ends.t_end[s] (slot boundaries of the compacted last layer's rows)
   bool trim_last = env_flag("TST_TRIM_LAST", true);   // "trim_last_token" (include/tst_hip.h tst_set_option; env TST_TRIM_LAST=0 starts with it off)
   int swr = [] { const char* e = getenv("TST_SWR"); return e ? atoi(e) & 3 : 3; }();   // "swiglu_rank": bit 0 the forward, bit 1 the backward fused SwiGLU + rank kernel (env TST_SWR)
-  bool lc_have = false, lc_on = false, lc_used = false, lc_active = false, lc_batch_ok = true;   // last-layer compaction (see lc_attn below): workspace there / switched on / this batch / now
+  bool lc_have = false, lc_on = false, lc_used = false, lc_batch_ok = true;   // last-layer compaction (see lc_attn below): workspace there / switched on / this batch
   int slot_r0[TST_MAX_STACK + 1] = {0};  // current batch: labelled rows of slot s are [slot_r0[s], slot_r0[s+1])
   std::vector<TrainableInfo> tinfo;
   long pack_max_elems = 0, pack_max_long = 0;
   float *clip_out = nullptr, *clip_partial = nullptr;  // device [2], [4096]
   // Which slots take an optimizer step and what their loss is normalised by. Default: a slot steps when it has labelled rows in the
   // batch and is normalised by that count. Gradient accumulation (tst_accumulate_async) and the stacked data-parallel step
-  // (tst_train_step_stacked_dp_async) give the count of the WHOLE accumulated / global batch per slot (items_override) instead.
+  // (tst_train_step_stacked_dp_async) give the count of the WHOLE accumulated / global batch per slot (backward()'s slot_items) instead.
   bool slot_steps[TST_MAX_STACK] = {false};
-  bool items_override_on = false;
-  int items_override[TST_MAX_STACK] = {0};
   // gradient accumulation (HF/trainer.py:1740-1758): tacc = running sum of the micro-batches' flat gradients, d_loss_acc = of their losses;
   // allocated by the first tst_accumulate_async of the context (LoRA: n_train floats; full fine-tune: another 4 B / parameter)
   float *tacc = nullptr, *d_loss_acc = nullptr;
@@ -275,8 +284,7 @@ struct tst_ctx {
   // Greedy generation (tst_generate_async; kernels in decode.hip, row map in host_logic.h plan_generate). Allocated by the first generation of the context,
   // for gen_cap_new new tokens per sequence; re-allocated behind a stream sync when a later call asks for more. gen_kv = K then V of layer 0, layer 1, ...:
   // [gen_rows, Hkv dh] each in the activation dtype. gen_dev = meta | prefill_rows [Tmax] | decode_rows; gen_tok / gen_logp = the steps' outputs [S, max_new].
-  // gen_mode: 0 = forward() is the graph every other entry point runs; 1 = a generation's prefill (RoPE as its own pass, k | v of every layer appended to the
-  // cache); 2 = a decode step (one row per sequence, positions from d_pos, attn_decode against the cache).
+  // forward() takes the pass of a generation as its GenPass argument (below).
   void* gen_kv = nullptr;
   int64_t gen_kv_bytes = 0, gen_dev_bytes = 0, gen_out_bytes = 0;
   long gen_rows = 0;
@@ -286,7 +294,6 @@ struct tst_ctx {
   int* h_gen = nullptr;         // pinned: staging image of gen_dev | tokens [Smax, cap_new] | logp [Smax, cap_new] of the pending generation
   hipEvent_t gen_evt = nullptr; // recorded behind the result copies: tst_generate_fetch waits for it, not for the stream
   int gen_S = -1, gen_new = 0;  // pending generation (-1: none)
-  int gen_mode = 0, gen_step = 0;
   std::vector<int> gen_eos;
   float* d_loss = nullptr;
   int cur_T = 0, cur_S = 0, cur_R = 0, cur_maxlen = 0, cur_items = 0;
@@ -339,6 +346,11 @@ struct CtxT : tst_ctx {
   AT *wpe = nullptr, *final_norm_b = nullptr;
   AT *embed = nullptr, *lm_head = nullptr, *lm_headT = nullptr, *final_norm = nullptr;
   std::vector<LayerT<AT>> layers;
+  // every tensor the model's state_dict names, built once at the end of build_ctx: tst_set_weight / tst_get_weight look a name up here, and the trainables of a
+  // full fine-tune (tst_trainable_info) are the entries that lie inside wb. rows / cols describe the device layout (a GPT-2 Conv1D weight: [out, in], the
+  // transpose of the HF tensor); alias: a second name of storage another entry owns (GPT-2's tied lm_head)
+  struct Named { std::string name; AT* ptr; int64_t rows, cols; bool conv1d, alias; };
+  std::vector<Named> named;
   AT* x_last = nullptr;  // output of the last layer
   // full fine-tune: wb = compute copy of all weights in ONE flat buffer laid out exactly like the fp32 master tp; wb0 = pristine snapshot
   AT *wb = nullptr, *wb0 = nullptr;
@@ -602,16 +614,44 @@ int run_gemm_tn(CtxT<AT>* ctx, const AT* P, long ldp, const AT* Q, long ldq, flo
   return rc;
 }
 
-// slot boundaries of the rows the current contraction runs over: tokens, or the compact labelled rows of the last layer
+// the K-major members of the 256x256 ping-pong tile (gemm_pp.hip; bf16 path): TN for dW = dy^T . x, NN for dX = dy . W. `site` names the caller in the error text
+inline int run_gemm_kmajor(tst_ctx* ctx, const GemmParams& p, bool on_side, int split, double flop, const char* site, bool shape_in_err = false) {
+  hipStream_t st = on_side ? ctx->side : ctx->stream;
+  const int slot = prof_begin(ctx, st, ctx->prof);
+  int used[2] = {5, 1};
+  const int rc = gemm_pp_kmajor(st, p, on_side ? ctx->side_slab : ctx->slab, on_side ? ctx->side_slab_bytes : ctx->slab_bytes, split, used);
+  prof_end(ctx, st, slot, used[0], used[1], flop);
+  if (rc != TST_OK && ctx->err.empty()) {
+    ctx->err = std::string("gemm_pp_kmajor (") + site + ") rc=" + std::to_string(rc);
+    if (shape_in_err) ctx->err += " M=" + std::to_string(p.M) + " N=" + std::to_string(p.N) + " K=" + std::to_string(p.K);
+  }
+  return rc;
+}
+
+// the rows a contraction runs over: the batch's token rows (slot boundaries slot_ends), or the compact labelled rows of the last layer (row_ends)
+struct Rows {
+  int n;
+  const SlotEnds* ends;
+  bool compact;
+};
+inline Rows token_rows(const tst_ctx* ctx) { return {ctx->cur_T, &ctx->slot_ends, false}; }
+inline Rows compact_rows(const tst_ctx* ctx) { return {ctx->cur_R, &ctx->row_ends, true}; }
+
+// the slot mask of a rank-axis operand: row t keeps the rank block (nmod * r columns) of its slot only. Stacked folds always; with one_slot_too (the fused norm /
+// SwiGLU rank kernels) also an unstacked context whose block is a multiple of 16 and <= 64 wide: one slot, the columns behind it are the packed operands' zero padding
 template <typename AT>
-const SlotEnds& ends_cur(const CtxT<AT>* ctx) { return ctx->lc_active ? ctx->row_ends : ctx->slot_ends; }
+void slot_mask(const tst_ctx* ctx, const LoraGroupT<AT>& g, const Rows& rows, bool one_slot_too, int& width, int& nslot, SlotEnds& ends) {
+  const int w = g.d.nmod * g.d.r;
+  if (ctx->ns > 1 || (one_slot_too && (w & 15) == 0 && w <= 64)) { width = w; nslot = ctx->ns > 1 ? ctx->ns : 1; }
+  if (ctx->ns > 1) ends = *rows.ends;
+}
 
 // stacked folds: u / du rows are zero outside their slot's rank block -- tell the projection tile, which then skips the K2 k-tiles of other slots
 // (TST_K2_SLOTS=0: A/B switch, every K2 k-tile runs)
 template <typename AT>
-void k2_slots(const CtxT<AT>* ctx, GemmParamsT<AT>& p, int w) {
+void k2_slots(const tst_ctx* ctx, GemmParamsT<AT>& p, const LoraGroupT<AT>& g, const Rows& rows) {
   static const bool on = env_flag("TST_K2_SLOTS", true);
-  if (on && ctx->ns > 1 && sizeof(AT) == 2) { p.k2_w = w; p.mask_nslot = ctx->ns; p.mask_ends = ends_cur(ctx); }
+  if (on && sizeof(AT) == 2) slot_mask(ctx, g, rows, false, p.k2_w, p.mask_nslot, p.mask_ends);
 }
 
 template <typename AT>
@@ -622,40 +662,38 @@ GemmParamsT<AT> gp(const AT* A, long lda, const AT* B, long ldb, void* C, long l
   return p;
 }
 
-// y[T,dout] = x.W^T (+ us.Bg^T) (+R)
 // SwiGLU fused with the rank-axis contraction that reads its result (swiglu_rank.hip): bf16 LoRA path with [gate | up] layout. ctx->swr (tst_set_option
 // "swiglu_rank", env TST_SWR): bit 0 the forward (act and us of the down projection), bit 1 the backward (dgu and du of the gate|up projection); default both;
 // 0 = the elementwise kernel + gemm_rank / gemm_nt
 template <typename AT>
-bool swr_setup(CtxT<AT>* ctx, const LoraGroupT<AT>& g, bool backward, int T, AT* C, SwiRank& r) {
+bool swr_setup(CtxT<AT>* ctx, const LoraGroupT<AT>& g, bool backward, const Rows& rows, AT* C, SwiRank& r) {
   if constexpr (sizeof(AT) != 2) return false;
   else {
     if (!(ctx->swr & (backward ? 2 : 1)) || ctx->gpt2 || ctx->full || !g.on || whatif()) return false;
     memset(&r, 0, sizeof(r));
     r.B = backward ? g.d.BgT : g.d.Ag; r.ldb = backward ? 2L * ctx->F : (long)ctx->F; r.C = C; r.N = g.d.RP;
     r.alpha = backward ? 1.0f : g.d.scale;
-    // the rank block of a slot: nmod * r columns; an unstacked context is one slot (the columns behind it, up to RP, are the padding of the packed operands: zeros)
-    const int w = g.d.nmod * g.d.r;
-    if (ctx->ns > 1 || ((w & 15) == 0 && w <= 64)) { r.mask_width = w; r.mask_nslot = ctx->ns > 1 ? ctx->ns : 1; }
-    if (ctx->ns > 1) r.mask_ends = ends_cur(ctx);
+    slot_mask(ctx, g, rows, true, r.mask_width, r.mask_nslot, r.mask_ends);
     // gate|up group: module 0 owns the gate rows, module 1 the up rows -- Bg is block diagonal, half of BgT's entries in a slot's rank block are zeros by construction
     r.block_diag = backward && r.mask_width && g.d.nmod == 2 && g.d.seg_row0[0] == 0 && g.d.seg_row1[0] == ctx->F && g.d.seg_row0[1] == ctx->F &&
                    g.d.seg_row1[1] == 2 * ctx->F;
-    return swiglu_rank_supported(T, ctx->F, r);
+    return swiglu_rank_supported(rows.n, ctx->F, r);
   }
 }
 
+// y[rows, dout] = x.W^T (+ us.Bg^T) (+R)
 template <typename AT>
-int linear_fwd(CtxT<AT>* ctx, const AT* x, int din, const AT* W, int dout, const LoraGroupT<AT>& g, AT* us, const AT* R, AT* y, int T,
-               const AT* bias = nullptr, bool us_done = false) {
+int linear_fwd(CtxT<AT>* ctx, const AT* x, const ProjT<AT>& P, AT* us, const AT* R, AT* y, const Rows& rows, const AT* bias = nullptr, bool us_done = false) {
+  const LoraGroupT<AT>& g = *P.g;
+  const int T = rows.n, din = P.din, dout = P.dout;
   if (g.on && !us_done) {   // us_done: the kernel that produced x has formed us = s x . Ag^T on the way (swiglu_rank_fwd)
     GemmParamsT<AT> q = gp<AT>(x, din, g.d.Ag, din, us, g.d.RP, T, g.d.RP, din);
     q.alpha = g.d.scale;
-    if (ctx->ns > 1) { q.mask_width = g.d.nmod * g.d.r; q.mask_nslot = ctx->ns; q.mask_ends = ends_cur(ctx); }   // applied where the output is rounded
+    slot_mask(ctx, g, rows, false, q.mask_width, q.mask_nslot, q.mask_ends);   // applied where the output is rounded
     if (!(whatif() & 8)) CTX_RC(run_gemm(ctx, q));
   }
-  GemmParamsT<AT> p = gp<AT>(x, din, W, din, y, dout, T, dout, din);
-  if (g.on) { p.A2 = us; p.lda2 = g.d.RP; p.B2 = g.d.Bg; p.ldb2 = g.d.RP; p.K2 = g.d.RP; k2_slots(ctx, p, g.d.nmod * g.d.r); }
+  GemmParamsT<AT> p = gp<AT>(x, din, P.W, din, y, dout, T, dout, din);
+  if (g.on) { p.A2 = us; p.lda2 = g.d.RP; p.B2 = g.d.Bg; p.ldb2 = g.d.RP; p.K2 = g.d.RP; k2_slots(ctx, p, g, rows); }
   p.R = R; p.ldr = dout;
   p.bias = bias;
   return run_gemm(ctx, p);
@@ -676,16 +714,26 @@ AT* du_target(CtxT<AT>* ctx, const LoraGroupT<AT>& g, int slot, bool* grouped_ou
   return (on_side || grouped) ? ctx->du4[slot] : ctx->du;
 }
 
+// elements of one layer's four projection matrices: a layer's share of the flat buffer of a full fine-tune
+inline int64_t layer_numel(const tst_ctx* ctx) {
+  int64_t n = 0;
+  for (int p = 0; p < 4; ++p) n += (int64_t)ctx->proj_dout[p] * ctx->proj_din[p];
+  return n;
+}
+// sums-of-squares slots of one weight-gradient matrix (tst_ctx::gn_partial): one per 256x256 tile + 16 per possible tail tile (at most 128)
+inline int64_t gn_slots(int dout, int din) { return (int64_t)tst_ceil_div(dout, 256) * tst_ceil_div(din, 256) + 2048; }
+
 template <typename AT>
-int linear_bwd(CtxT<AT>* ctx, const AT* dy, int dout, const AT* x, int din, const AT* W, const AT* WT, const LoraGroupT<AT>& g, const AT* us, AT* dx, int T,
-               float* dW = nullptr, int slot = 0, bool need_dx = true, bool du_done = false) {
+int linear_bwd(CtxT<AT>* ctx, const AT* dy, const AT* x, const ProjT<AT>& P, const AT* us, AT* dx, const Rows& rows, float* dW = nullptr, int slot = 0,
+               bool need_dx = true, bool du_done = false) {
+  const LoraGroupT<AT>& g = *P.g;
+  const int T = rows.n, din = P.din, dout = P.dout;
   // full fine-tune: dW[dout,din] = dy^T . x (fp32, written straight into the flat gradient buffer). Both factors are large and the contraction axis
   // (tokens) is short. Round 5: the TN member of the 256x256 ping-pong tile contracts the row-major activations as they are (rows >= T of the last k-tile
   // are out of range of its buffer descriptor and read as zeros). Before (ctx->kmajor bit 1 off, strict mode): both activations transposed into zero-padded
   // [cols, Tp] copies (~0.3 GB of traffic per layer) + the NT member on them; the 128x128 TN tiles of gemm.hip reach only ~320 TFLOP/s on these shapes.
   if (dW) {
-    // slots for this matrix's sums of squares: one per 256x256 tile + 16 per possible tail tile (at most 128)
-    const int64_t slots = (int64_t)tst_ceil_div(dout, 256) * tst_ceil_div(din, 256) + 2048;
+    const int64_t slots = gn_slots(dout, din);
     float* ssq = (ctx->gn_fused && ctx->gn_used + slots <= ctx->gn_cap) ? ctx->gn_partial + ctx->gn_used : nullptr;
     if (!ssq) ctx->gn_fused = false;
     ctx->gn_used += slots;
@@ -706,12 +754,7 @@ int linear_bwd(CtxT<AT>* ctx, const AT* dy, int dout, const AT* x, int din, cons
         GemmParams w = gp<AT>(dy, dout, x, din, dW, din, dout, din, roundup(T, 64));
         w.ta = 1; w.tb = 1; w.kvalid = T; w.out_f32 = 1; w.sumsq = ssq; w.no_tail = 1;
         if (gemm_pp_kmajor_supported(w)) {
-          const int pslot = prof_begin(ctx, wst, ctx->prof);
-          int used[2] = {5, 1};
-          const int rc = gemm_pp_kmajor(wst, w, ws ? ctx->side_slab : ctx->slab, ws ? ctx->side_slab_bytes : ctx->slab_bytes, 1, used);
-          prof_end(ctx, wst, pslot, used[0], used[1], 2.0 * dout * din * (double)T);
-          if (rc != TST_OK && ctx->err.empty()) ctx->err = "gemm_pp_kmajor (TN) rc=" + std::to_string(rc);
-          CTX_RC(rc);
+          CTX_RC(run_gemm_kmajor(ctx, w, ws, 1, 2.0 * dout * din * (double)T, "TN"));
           tn_done = true;
           in_epilogue = true;   // (unsplit: the tile epilogues wrote the sums of squares)
         }
@@ -738,7 +781,7 @@ int linear_bwd(CtxT<AT>* ctx, const AT* dy, int dout, const AT* x, int din, cons
     const int RP = g.d.RP;
     // du[T,RP] = dy . Bg  (on the dX chain: it is the second K segment of the dX contraction); du_done: the kernel that produced dy has formed it (swiglu_rank_bwd)
     GemmParamsT<AT> b = gp<AT>(dy, dout, g.d.BgT, dout, du, RP, T, RP, dout);
-    if (ctx->ns > 1) { b.mask_width = g.d.nmod * g.d.r; b.mask_nslot = ctx->ns; b.mask_ends = ends_cur(ctx); }
+    slot_mask(ctx, g, rows, false, b.mask_width, b.mask_nslot, b.mask_ends);
     if (!du_done && !(whatif() & 8)) CTX_RC(run_gemm(ctx, b));
     // adapter gradients contract over the token axis of both operands: TN form, no transposed copies; off the dX chain
     if (on_side) {
@@ -781,23 +824,21 @@ int linear_bwd(CtxT<AT>* ctx, const AT* dy, int dout, const AT* x, int din, cons
   }
   if (!need_dx) return TST_OK;   // (the first layer of a LoRA fine-tune: nothing trainable lies below its q|k|v projection)
   if constexpr (sizeof(AT) == 2) {
-    if (!WT) {   // full fine-tune without W^T copies (ctx->kmajor bit 0): dx = dy . W on the NN member, W[dout][din] as it is stored
-      GemmParams q = gp<AT>(dy, dout, W, din, dx, din, T, din, dout);
+    if (!P.WT) {   // full fine-tune without W^T copies (ctx->kmajor bit 0): dx = dy . W on the NN member, W[dout][din] as it is stored
+      GemmParams q = gp<AT>(dy, dout, P.W, din, dx, din, T, din, dout);
       q.tb = 1; q.no_tail = 1;
       static const int fsk = [] { const char* e = getenv("TST_FULL_SPLITK"); return e ? atoi(e) : 2; }();
       if (!(fsk & 2)) q.no_splitk = 1;
-      const int pslot = prof_begin(ctx, ctx->stream, ctx->prof);
-      int used[2] = {5, 1};
-      const int rc = gemm_pp_kmajor(ctx->stream, q, ctx->slab, ctx->slab_bytes, -1, used);
-      prof_end(ctx, ctx->stream, pslot, used[0], used[1], 2.0 * T * din * (double)dout);
-      if (rc != TST_OK && ctx->err.empty()) ctx->err = "gemm_pp_kmajor (NN) rc=" + std::to_string(rc) + " M=" + std::to_string(T) + " N=" + std::to_string(din) + " K=" + std::to_string(dout);
-      return rc;
+      return run_gemm_kmajor(ctx, q, false, -1, 2.0 * T * din * (double)dout, "NN", true);
     }
   }
-  GemmParamsT<AT> p = gp<AT>(dy, dout, WT, dout, dx, din, T, din, dout);
-  if (g.on) { p.A2 = du; p.lda2 = g.d.RP; p.B2 = g.d.AgT; p.ldb2 = g.d.RP; p.K2 = g.d.RP; k2_slots(ctx, p, g.d.nmod * g.d.r); }
+  GemmParamsT<AT> p = gp<AT>(dy, dout, P.WT, dout, dx, din, T, din, dout);
+  if (g.on) { p.A2 = du; p.lda2 = g.d.RP; p.B2 = g.d.AgT; p.ldb2 = g.d.RP; p.K2 = g.d.RP; k2_slots(ctx, p, g, rows); }
   return run_gemm(ctx, p);
 }
+
+// what a batch of this context may hold (host_logic.h: plan_batch, plan_generate and the staging / cache layouts)
+inline tsthost::BatchLimits batch_limits(const tst_ctx* ctx) { return {ctx->Tmax, ctx->Smax, ctx->Rmax, ctx->V, ctx->cfg.max_position, ctx->ns}; }
 
 int upload_batch(tst_ctx* ctx, const tst_batch* b, bool need_labels, const int32_t* rows, int n_rows) {
   // validation, trimmed token list, positions, labelled-row map and slot boundaries: tsthost::plan_batch (host_logic.h; pure host arithmetic on the caller's
@@ -811,7 +852,7 @@ int upload_batch(tst_ctx* ctx, const tst_batch* b, bool need_labels, const int32
   ctx->cur_stage = hs;
   int* h_ids = hs;
   int* h_pos = h_ids + ctx->Tmax;
-  const tsthost::BatchLimits lim = {ctx->Tmax, ctx->Smax, ctx->Rmax, ctx->V, ctx->cfg.max_position, ctx->ns};
+  const tsthost::BatchLimits lim = batch_limits(ctx);
   tsthost::BatchPlan plan;
   {
     std::string perr;
@@ -867,7 +908,7 @@ int norm_bwd(CtxT<AT>* ctx, const AT* dy, const AT* x, const float* stats, const
 // Returns true when the fused kernel ran (the caller then passes us_done to linear_fwd). ctx->nrk ("norm_rank", env TST_NRK): 1 = on (default), 0 = the norm and
 // gemm_rank as two launches; xn and rstd are bit-identical either way (rmsnorm_fwd routes the same widths through the same kernel), us sums the same products in another order
 template <typename AT>
-bool norm_rank_fwd(CtxT<AT>* ctx, const AT* x, const AT* w, AT* y, float* stats, int T, const LoraGroupT<AT>& g, AT* us, int* rc_out) {
+bool norm_rank_fwd(CtxT<AT>* ctx, const AT* x, const AT* w, AT* y, float* stats, const Rows& rows, const LoraGroupT<AT>& g, AT* us, int* rc_out) {
   *rc_out = TST_OK;
   if constexpr (sizeof(AT) != 2) return false;
   else {
@@ -875,10 +916,9 @@ bool norm_rank_fwd(CtxT<AT>* ctx, const AT* x, const AT* w, AT* y, float* stats,
     NormRank r;
     memset(&r, 0, sizeof(r));
     r.B = g.d.Ag; r.ldb = ctx->d; r.C = us; r.N = g.d.RP; r.alpha = g.d.scale;
-    const int w_ = g.d.nmod * g.d.r;
-    if (ctx->ns > 1 || ((w_ & 15) == 0 && w_ <= 64)) { r.mask_width = w_; r.mask_nslot = ctx->ns > 1 ? ctx->ns : 1; }
-    if (ctx->ns > 1) r.mask_ends = ends_cur(ctx);
-    else r.mask_ends.t_end[0] = T;
+    const int T = rows.n;
+    slot_mask(ctx, g, rows, true, r.mask_width, r.mask_nslot, r.mask_ends);
+    if (ctx->ns == 1) r.mask_ends.t_end[0] = T;   // (one slot: all rows)
     if (!rmsnorm_rank_supported(T, ctx->d, &r)) return false;
     const int slot = prof_begin(ctx, ctx->stream, ctx->prof_hbm);
     *rc_out = rmsnorm_rank_fwd(ctx->stream, x, w, y, stats, T, ctx->d, ctx->cfg.rms_norm_eps, &r);
@@ -938,16 +978,70 @@ bool rope_fused(const CtxT<AT>* ctx) {
   return false;
 }
 
+// The half of a layer behind the attention -- o projection, MLP norm, gate|up projection, SwiGLU / GELU, down projection -- runs on the layer's token rows or,
+// for the compacted last layer, on the gathered labelled rows: the same schedule on another set of buffers.
+template <typename AT>
+struct TailBufsT {
+  AT *attn, *x_in, *hmid, *xn2, *gu, *act, *us_o, *us_gu, *us_d;   // stash
+  float* rstd2;
+  AT* out;                                  // forward: the layer's output rows
+  AT *dout, *dact, *dgu, *dxn, *dH, *dattn; // backward: gradient of the output rows (read) and the scratch down to the attention output's gradient
+};
+template <typename AT>
+TailBufsT<AT> token_tail(CtxT<AT>* ctx, LayerT<AT>& A, AT* x_in = nullptr, AT* x_out = nullptr) {   // (backward reads neither x_in nor out)
+  return {A.attn, x_in, A.hmid, A.xn2, A.gu, A.act, A.us_o, A.us_gu, A.us_d, A.rstd2, x_out, ctx->dX, ctx->dact, ctx->dgu, ctx->dxn, ctx->dH, ctx->dattn_b};
+}
+// compact rows: the layer's output lands in xg, where head_forward / the final norm's backward expect the head's input rows, and dxg IS the gradient of those rows
+template <typename AT>
+TailBufsT<AT> compact_tail(CtxT<AT>* ctx) {
+  return {ctx->lc_attn, ctx->lc_xin, ctx->lc_hmid, ctx->lc_xn2, ctx->lc_gu, ctx->lc_act, ctx->lc_us_o, ctx->lc_us_gu, ctx->lc_us_d, ctx->lc_rstd2, ctx->xg,
+          ctx->dxg, ctx->lc_dact, ctx->lc_dgu, ctx->lc_dxn, ctx->lc_dH, ctx->lc_dattn};
+}
+
+// hmid = x_in + o(attn); out = hmid + down(act(gate|up(norm(hmid))))
+template <typename AT>
+int tail_fwd(CtxT<AT>* ctx, LayerT<AT>& W, const Rows& rows, const TailBufsT<AT>& B) {
+  hipStream_t st = ctx->stream;
+  const int n = rows.n;
+  CTX_RC(linear_fwd<AT>(ctx, B.attn, W.proj[P_O], B.us_o, B.x_in, B.hmid, rows, W.bo));
+  bool u_gu = false;
+  if (!rows.compact) {   // compact rows: always the plain norm kernel followed by the rank contraction (the fused kernel there is an unmeasured question)
+    int nrc = TST_OK;
+    u_gu = norm_rank_fwd<AT>(ctx, B.hmid, W.mlp_norm, B.xn2, B.rstd2, rows, W.g_gu, B.us_gu, &nrc);   // xn2 AND the gate|up group's u
+    CTX_RC(nrc);
+  }
+  if (!u_gu && !(whatif() & 1)) CTX_RC(norm_fwd<AT>(ctx, B.hmid, W.mlp_norm, W.mlp_norm_b, B.xn2, B.rstd2, n));
+  CTX_RC(linear_fwd<AT>(ctx, B.xn2, W.proj[P_GU], B.us_gu, nullptr, B.gu, rows, W.bgu, u_gu));
+  bool us_done = false;
+  if (ctx->gpt2) CTX_RC(gelu_fwd<AT>(st, B.gu, B.act, (long)n * ctx->F));
+  else {
+    const int slot = prof_begin(ctx, st, ctx->prof_hbm && !rows.compact);   // compact rows: no bracket (the SwiGLU class of the measurement hooks counts token-row launches)
+    SwiRank sr;
+    if (swr_setup<AT>(ctx, W.g_d, false, rows, B.us_d, sr)) {   // act AND the down projection's us = s act . Ag^T in one pass over gate | up
+      if constexpr (sizeof(AT) == 2) CTX_RC(swiglu_rank_fwd(st, B.gu, B.act, n, ctx->F, sr));
+      us_done = true;
+    } else if (!(whatif() & 4)) CTX_RC(swiglu_fwd<AT>(st, B.gu, B.act, n, ctx->F));
+    prof_end(ctx, st, slot, PROF_SWIGLU, 1, 3.0 * n * ctx->F * sizeof(AT));   // read gate, up; write act
+  }
+  return linear_fwd<AT>(ctx, B.act, W.proj[P_D], B.us_d, B.hmid, B.out, rows, W.bd, us_done);
+}
+
+// what a generation asks of forward(): mode 0 = the graph every other entry point runs; 1 = the prefill (RoPE as its own pass, k | v of every layer appended to
+// the cache); 2 = decode step `step` (one row per sequence, positions from d_pos, attn_decode against the cache)
+struct GenPass {
+  int mode = 0, step = 0;
+};
+
 // forward through the decoder stack; stash=true keeps per-layer activations for the backward pass
 template <typename AT>
-int forward(CtxT<AT>* ctx, bool stash) {
+int forward(CtxT<AT>* ctx, bool stash, GenPass gen = {}) {
   const int T = ctx->cur_T, d = ctx->d;
   hipStream_t st = ctx->stream;
   const float scale = 1.0f / sqrtf((float)ctx->dh);
+  const Rows rows = token_rows(ctx);
   LayerT<AT>& L0 = ctx->layers[0];
   // (R rows of ~T / 40 in the diagnostic's batches; a batch labelled on most of its tokens gains nothing from the gathers)
   ctx->lc_used = ctx->lc_on && ctx->lc_batch_ok && ctx->cur_R > 0 && 2 * ctx->cur_R <= T;
-  ctx->lc_active = false;
   whatif_tick();   // (process-wide: the bench's contexts step in turn)
   CTX_RC(opt_need(ctx, 1));   // norm vectors / biases and the embedding side of a pending optimizer step
   if (ctx->gpt2) CTX_RC(embed_pos_fwd<AT>(st, ctx->d_ids, ctx->d_pos, ctx->embed, ctx->wpe, L0.x_in, T, d, ctx->V, ctx->npos));
@@ -961,15 +1055,15 @@ int forward(CtxT<AT>* ctx, bool stash) {
     bool u_qkv = false;
     {
       int nrc = TST_OK;
-      u_qkv = norm_rank_fwd<AT>(ctx, x_in, W.attn_norm, A.xn1, A.rstd1, T, W.g_qkv, A.us_qkv, &nrc);   // xn1 AND the q|k|v group's u in one pass
+      u_qkv = norm_rank_fwd<AT>(ctx, x_in, W.attn_norm, A.xn1, A.rstd1, rows, W.g_qkv, A.us_qkv, &nrc);   // xn1 AND the q|k|v group's u in one pass
       CTX_RC(nrc);
     }
     if (!u_qkv && !(whatif() & 1)) CTX_RC(norm_fwd<AT>(ctx, x_in, W.attn_norm, W.attn_norm_b, A.xn1, A.rstd1, T));
-    CTX_RC(linear_fwd<AT>(ctx, A.xn1, d, W.Wqkv, ctx->dqkv, W.g_qkv, A.us_qkv, nullptr, A.qkv, T, W.bqkv, u_qkv));
+    CTX_RC(linear_fwd<AT>(ctx, A.xn1, W.proj[P_QKV], A.us_qkv, nullptr, A.qkv, rows, W.bqkv, u_qkv));
     // RoPE: inside the attention kernels where they can (bf16 path, sequences <= 128 tokens: q and k then stay UN-rotated in the stash and
     // the backward kernel rotates dq / dk back itself), else as a pass of its own over q and k
     // (a generation keeps the rotation a pass of its own: the cache takes k as attention reads it, and kv_append stays a copy)
-    const bool rope_in = !ctx->gpt2 && !ctx->gen_mode && rope_fused(ctx);
+    const bool rope_in = !ctx->gpt2 && !gen.mode && rope_fused(ctx);
     if (ctx->qk_norm) {
       // Qwen3: head norm in place on q|k, and the rotation in the same traversal whenever RoPE is a pass of its own (q|k read and written once, not twice)
       const int slot = prof_begin(ctx, st, ctx->prof_hbm);
@@ -978,21 +1072,21 @@ int forward(CtxT<AT>* ctx, bool stash) {
       prof_end(ctx, st, slot, PROF_NORM, 1, (stash ? 3.0 : 2.0) * T * (ctx->dq + ctx->dkv) * sizeof(AT));
     } else
     if (!ctx->gpt2 && !rope_in) CTX_RC(rope_apply<AT>(st, A.qkv, ctx->d_pos, ctx->cosT, ctx->sinT, T, ctx->H + ctx->Hkv, ctx->dh, ctx->dqkv, 0));
-    if (ctx->gen_mode) {
+    if (gen.mode) {
       // generation: this layer's k | v rows join the cache here -- behind the head norm and RoPE, before the activation slot is reused by the next layer
       const long wkv = (long)ctx->Hkv * ctx->dh;
       AT* kc = (AT*)ctx->gen_kv + (long)l * 2 * ctx->gen_rows * wkv;
       AT* vc = kc + ctx->gen_rows * wkv;
       const int S = ctx->cur_S;
-      const int* rows = ctx->gen_dev + (3 + 2 * ctx->Smax) + (ctx->gen_mode == 1 ? 0L : ctx->Tmax + (long)(ctx->gen_step - 1) * S);
-      CTX_RC(kv_append<AT>(st, A.qkv, ctx->dqkv, ctx->dq, rows, kc, vc, T, ctx->Hkv, ctx->dh, ctx->gen_rows));
-      if (ctx->gen_mode == 2) {
+      const int* krows = ctx->gen_dev + (3 + 2 * ctx->Smax) + (gen.mode == 1 ? 0L : ctx->Tmax + (long)(gen.step - 1) * S);
+      CTX_RC(kv_append<AT>(st, A.qkv, ctx->dqkv, ctx->dq, krows, kc, vc, T, ctx->Hkv, ctx->dh, ctx->gen_rows));
+      if (gen.mode == 2) {
         const int slot = prof_begin(ctx, st, ctx->prof_hbm);
-        CTX_RC(attn_decode<AT>(st, A.qkv, ctx->dqkv, kc, vc, ctx->gen_dev, S, ctx->gen_step, A.attn, ctx->dattn, ctx->H, ctx->Hkv, ctx->dh, scale, ctx->gen_rows));
+        CTX_RC(attn_decode<AT>(st, A.qkv, ctx->dqkv, kc, vc, ctx->gen_dev, S, gen.step, A.attn, ctx->dattn, ctx->H, ctx->Hkv, ctx->dh, scale, ctx->gen_rows));
         prof_end(ctx, st, slot, PROF_ATTN, 1, 4.0 * ctx->cur_sumsq_len * ctx->H * ctx->dh);   // q . K^T + P . V over the cached keys (cur_sumsq_len = their count)
       }
     }
-    if (ctx->gen_mode != 2) {
+    if (gen.mode != 2) {
       const int slot = prof_begin(ctx, st, ctx->prof_hbm);
       if (whatif() & 2) {
       } else if constexpr (sizeof(AT) == 2)
@@ -1004,49 +1098,13 @@ int forward(CtxT<AT>* ctx, bool stash) {
     }
     if (l == ctx->L - 1 && ctx->lc_used) {
       // last layer: everything behind the attention is row-wise and only the head's rows are read (head_forward gathers exactly these): o projection and
-      // MLP on the R gathered rows; the layer's output lands in xg, where head_forward / the final norm's backward expect the head's input rows
-      const int R = ctx->cur_R;
-      CTX_RC(gather_rows<AT>(st, A.attn, ctx->d_lab_idx, ctx->lc_attn, R, ctx->dattn, 0));
-      CTX_RC(gather_rows<AT>(st, x_in, ctx->d_lab_idx, ctx->lc_xin, R, d, 0));
-      ctx->lc_active = true;
-      int rc = linear_fwd<AT>(ctx, ctx->lc_attn, ctx->dattn, W.Wo, d, W.g_o, ctx->lc_us_o, ctx->lc_xin, ctx->lc_hmid, R, W.bo);
-      if (rc == TST_OK) rc = norm_fwd<AT>(ctx, ctx->lc_hmid, W.mlp_norm, W.mlp_norm_b, ctx->lc_xn2, ctx->lc_rstd2, R);
-      if (rc == TST_OK) rc = linear_fwd<AT>(ctx, ctx->lc_xn2, d, W.Wgu, ctx->Fgu, W.g_gu, ctx->lc_us_gu, nullptr, ctx->lc_gu, R, W.bgu);
-      bool us_done = false;
-      if (rc == TST_OK) {
-        SwiRank sr;
-        if (ctx->gpt2) rc = gelu_fwd<AT>(st, ctx->lc_gu, ctx->lc_act, (long)R * ctx->F);
-        else if (swr_setup<AT>(ctx, W.g_d, false, R, ctx->lc_us_d, sr)) {
-          if constexpr (sizeof(AT) == 2) rc = swiglu_rank_fwd(st, ctx->lc_gu, ctx->lc_act, R, ctx->F, sr);
-          us_done = true;
-        } else rc = swiglu_fwd<AT>(st, ctx->lc_gu, ctx->lc_act, R, ctx->F);
-      }
-      if (rc == TST_OK) rc = linear_fwd<AT>(ctx, ctx->lc_act, ctx->F, W.Wd, d, W.g_d, ctx->lc_us_d, ctx->lc_hmid, ctx->xg, R, W.bd, us_done);
-      ctx->lc_active = false;
-      CTX_RC(rc);
-      break;
+      // MLP on the R gathered rows
+      CTX_RC(gather_rows<AT>(st, A.attn, ctx->d_lab_idx, ctx->lc_attn, ctx->cur_R, ctx->dattn, 0));
+      CTX_RC(gather_rows<AT>(st, x_in, ctx->d_lab_idx, ctx->lc_xin, ctx->cur_R, d, 0));
+      CTX_RC(tail_fwd<AT>(ctx, W, compact_rows(ctx), compact_tail(ctx)));
+    } else {
+      CTX_RC(tail_fwd<AT>(ctx, W, rows, token_tail(ctx, A, x_in, x_out)));
     }
-    CTX_RC(linear_fwd<AT>(ctx, A.attn, ctx->dattn, W.Wo, d, W.g_o, A.us_o, x_in, A.hmid, T, W.bo));
-    bool u_gu = false;
-    {
-      int nrc = TST_OK;
-      u_gu = norm_rank_fwd<AT>(ctx, A.hmid, W.mlp_norm, A.xn2, A.rstd2, T, W.g_gu, A.us_gu, &nrc);   // xn2 AND the gate|up group's u
-      CTX_RC(nrc);
-    }
-    if (!u_gu && !(whatif() & 1)) CTX_RC(norm_fwd<AT>(ctx, A.hmid, W.mlp_norm, W.mlp_norm_b, A.xn2, A.rstd2, T));
-    CTX_RC(linear_fwd<AT>(ctx, A.xn2, d, W.Wgu, ctx->Fgu, W.g_gu, A.us_gu, nullptr, A.gu, T, W.bgu, u_gu));
-    bool us_done = false;
-    if (ctx->gpt2) CTX_RC(gelu_fwd<AT>(st, A.gu, A.act, (long)T * ctx->F));
-    else {
-      const int slot = prof_begin(ctx, st, ctx->prof_hbm);
-      SwiRank sr;
-      if (swr_setup<AT>(ctx, W.g_d, false, T, A.us_d, sr)) {   // act AND the down projection's us = s act . Ag^T in one pass over gate | up
-        if constexpr (sizeof(AT) == 2) CTX_RC(swiglu_rank_fwd(st, A.gu, A.act, T, ctx->F, sr));
-        us_done = true;
-      } else if (!(whatif() & 4)) CTX_RC(swiglu_fwd<AT>(st, A.gu, A.act, T, ctx->F));
-      prof_end(ctx, st, slot, PROF_SWIGLU, 1, 3.0 * T * ctx->F * sizeof(AT));   // read gate, up; write act
-    }
-    CTX_RC(linear_fwd<AT>(ctx, A.act, ctx->F, W.Wd, d, W.g_d, A.us_d, A.hmid, x_out, T, W.bd, us_done));
   }
   return TST_OK;
 }
@@ -1103,9 +1161,9 @@ int regions_join(CtxT<AT>* ctx) {
   return TST_OK;
 }
 
-// the collected adapter-gradient contractions of one layer, as one grouped launch (bf16 path only: tn_pending stays empty otherwise)
+// the collected adapter-gradient contractions of one layer, as one grouped launch (bf16 path only: tn_pending stays empty otherwise); rows: what they contract over
 template <typename AT>
-int flush_tn(CtxT<AT>* ctx) {
+int flush_tn(CtxT<AT>* ctx, const Rows& rows) {
   if (ctx->tn_pending.empty() && ctx->tns_pending.empty()) return TST_OK;
   if (whatif() & 16) { ctx->tn_pending.clear(); ctx->tns_pending.clear(); ctx->tn_pending_flop = 0; return TST_OK; }
   int rc = TST_OK;
@@ -1114,7 +1172,7 @@ int flush_tn(CtxT<AT>* ctx) {
     const int slot = prof_begin(ctx, st, ctx->prof);
     for (size_t i = 0; i < ctx->tns_pending.size() && rc == TST_OK; i += TST_MAX_GROUPED) {
       const size_t n = ctx->tns_pending.size() - i < TST_MAX_GROUPED ? ctx->tns_pending.size() - i : TST_MAX_GROUPED;
-      rc = gemm_tns_grouped(st, ctx->tns_pending.data() + i, (int)n, ctx->ns, ends_cur(ctx));
+      rc = gemm_tns_grouped(st, ctx->tns_pending.data() + i, (int)n, ctx->ns, *rows.ends);
     }
     for (size_t i = 0; i < ctx->tn_pending.size() && rc == TST_OK; i += TST_MAX_GROUPED) {
       const size_t n = ctx->tn_pending.size() - i < TST_MAX_GROUPED ? ctx->tn_pending.size() - i : TST_MAX_GROUPED;
@@ -1129,8 +1187,52 @@ int flush_tn(CtxT<AT>* ctx) {
   return rc;
 }
 
+// full fine-tune: the gradient of weight tensor w lives at tg + (w - wb) (the flat buffers share one layout); nullptr otherwise
 template <typename AT>
-int backward(CtxT<AT>* ctx, int num_items) {
+float* grad_of(CtxT<AT>* ctx, const AT* w) { return (ctx->full && w) ? ctx->tg + (w - ctx->wb) : nullptr; }
+
+// backward of tail_fwd: down projection, SwiGLU / GELU, gate|up projection, MLP norm (+ the residual), o projection; leaves dH and the attention output's gradient
+template <typename AT>
+int tail_bwd(CtxT<AT>* ctx, LayerT<AT>& W, const Rows& rows, const TailBufsT<AT>& B) {
+  hipStream_t st = ctx->stream;
+  const int n = rows.n, d = ctx->d;
+  // compact rows are LoRA only (backward(): lc = lc_used && !full): no bias column sums, no dW, no ndw_wait, no norm_bwd_dw
+  const bool full = ctx->full && !rows.compact;
+  auto gof = [&](const AT* w) -> float* { return full ? grad_of(ctx, w) : nullptr; };
+  // MLP block: out = hmid + down(act)
+  if (full && W.bd) CTX_RC(colsum<AT>(st, B.dout, d, gof(W.bd), n, d, ctx->colred_ws));
+  CTX_RC(linear_bwd<AT>(ctx, B.dout, B.act, W.proj[P_D], B.us_d, B.dact, rows, gof(W.proj[P_D].W), 0));
+  bool du_done = false;
+  if (ctx->gpt2) CTX_RC(gelu_bwd<AT>(st, B.dact, B.gu, B.dgu, (long)n * ctx->F));
+  else {
+    const int slot = prof_begin(ctx, st, ctx->prof_hbm && !rows.compact);   // compact rows: no bracket (as in tail_fwd)
+    SwiRank sr;
+    if (swr_setup<AT>(ctx, W.g_gu, true, rows, du_target(ctx, W.g_gu, 1), sr)) {   // dgu AND the gate|up projection's du = dgu . Bg in one pass
+      if constexpr (sizeof(AT) == 2) CTX_RC(swiglu_rank_bwd(st, B.dact, B.gu, B.dgu, n, ctx->F, sr));
+      du_done = true;
+    } else if (!(whatif() & 4)) CTX_RC(swiglu_bwd<AT>(st, B.dact, B.gu, B.dgu, n, ctx->F));
+    prof_end(ctx, st, slot, PROF_SWIGLU, 1, 5.0 * n * ctx->F * sizeof(AT));   // read dact, gate, up; write dgate, dup
+  }
+  if (full && W.bgu) CTX_RC(colsum<AT>(st, B.dgu, ctx->Fgu, gof(W.bgu), n, ctx->Fgu, ctx->colred_ws));
+  if (full) CTX_RC(ndw_wait(ctx, 1));   // (the previous layer's attention-norm reduction on the side stream reads dxn, which the contraction below overwrites)
+  CTX_RC(linear_bwd<AT>(ctx, B.dgu, B.xn2, W.proj[P_GU], B.us_gu, B.dxn, rows, gof(W.proj[P_GU].W), 1, true, du_done));
+  {
+    int frc = TST_OK;
+    if (!norm_bwd_dw<AT>(ctx, B.dxn, B.hmid, B.rstd2, W.mlp_norm, B.dout, B.dH, gof(W.mlp_norm), n, &frc)) {
+      if (full) CTX_RC(norm_dw<AT>(ctx, B.dxn, B.hmid, B.rstd2, gof(W.mlp_norm), gof(W.mlp_norm_b), n, 0));
+      CTX_RC(norm_bwd<AT>(ctx, B.dxn, B.hmid, B.rstd2, W.mlp_norm, B.dout, B.dH, n));
+    }
+    CTX_RC(frc);
+  }
+  // attention block: hmid = x_in + o(attn)
+  if (full && W.bo) CTX_RC(colsum<AT>(st, B.dH, d, gof(W.bo), n, d, ctx->colred_ws));
+  return linear_bwd<AT>(ctx, B.dH, B.attn, W.proj[P_O], B.us_o, B.dattn, rows, gof(W.proj[P_O].W), 2);
+}
+
+// num_items: what the loss is normalised by (one slot); slot_items: per-slot counts of a stacked context (nullptr: every slot by its own labelled rows in this
+// batch). reduce_regions: a data-parallel full fine-tune's step -- the gradient regions are all-reduced on the communication stream as backward finishes them
+template <typename AT>
+int backward(CtxT<AT>* ctx, int num_items, const int32_t* slot_items = nullptr, bool reduce_regions = false) {
   const int T = ctx->cur_T, d = ctx->d, R = ctx->cur_R;
   hipStream_t st = ctx->stream;
   const float scale = 1.0f / sqrtf((float)ctx->dh);
@@ -1144,10 +1246,10 @@ int backward(CtxT<AT>* ctx, int num_items) {
   ctx->tn_pending.clear();   // (a previous backward that failed half-way may have left entries)
   ctx->tns_pending.clear();
   ctx->tn_pending_flop = 0;
-  // full fine-tune: gradient of weight tensor w lives at tg + (w - wb) (the flat buffers share one layout)
-  auto gof = [&](const AT* w) -> float* { return (full && w) ? ctx->tg + (w - ctx->wb) : nullptr; };
+  auto gof = [&](const AT* w) -> float* { return grad_of(ctx, w); };
+  const Rows rows = token_rows(ctx);
   if (full) {
-    ctx->gn_fused = ctx->gn_partial != nullptr && !ctx->dp_in_step;
+    ctx->gn_fused = ctx->gn_partial != nullptr && !reduce_regions;
     ctx->gn_used = 0;
     if (ctx->gn_fused) CTX_HIP(hipMemsetAsync(ctx->gn_partial, 0, (size_t)ctx->gn_cap * sizeof(float), st));
     // regions that are accumulated with atomics start from zero: embedding rows and the norm vectors
@@ -1165,7 +1267,7 @@ int backward(CtxT<AT>* ctx, int num_items) {
     for (int sl = 0; sl < ctx->ns; ++sl) {
       const int r0 = ctx->slot_r0[sl], Rs = ctx->slot_r0[sl + 1] - r0;
       if (Rs <= 0) continue;
-      const float inv = 1.0f / (float)(ctx->items_override_on ? ctx->items_override[sl] : Rs);   // (checked > 0 by the caller)
+      const float inv = 1.0f / (float)(slot_items ? slot_items[sl] : Rs);   // (checked > 0 by the caller)
       CTX_RC(logit_rows<AT>(st, ctx->logits + (long)r0 * ctx->Vp, ctx->Vp, ctx->d_targets + r0, Rs, ctx->V, ctx->stats + 4L * r0, ctx->dlogits + (long)r0 * ctx->Vp,
                         ctx->Vp, inv, nullptr, 0, nullptr));
       CTX_RC(loss_reduce(st, ctx->stats + 4L * r0, Rs, inv, ctx->d_loss + sl));
@@ -1173,7 +1275,7 @@ int backward(CtxT<AT>* ctx, int num_items) {
   }
   // d lm_head[V,d] = dlogits^T . xf   (contraction over the labelled rows)
   if (full) CTX_RC(run_gemm_tn<AT>(ctx, ctx->dlogits, ctx->Vp, ctx->xf, d, gof(ctx->lm_head), d, ctx->Vp, d, R, 1.0f));
-  const bool regions = full && ctx->dp_in_step && !ctx->dp_regions.empty();
+  const bool regions = full && reduce_regions && !ctx->dp_regions.empty();
   const size_t r_head = (regions && !ctx->gpt2) ? 1 : 0;   // region 0 = lm_head (a tied head goes with the embedding, at the end)
   if (regions) { ctx->dp_next = 0; CTX_RC(region_done(ctx, r_head)); }
   // d xf = dlogits . lm_head
@@ -1185,12 +1287,7 @@ int backward(CtxT<AT>* ctx, int num_items) {
       const int tiles = tst_ceil_div(R, 256) * tst_ceil_div(d, 256);
       int sk = 256 / tiles;
       sk = sk < 1 ? 1 : (sk > 16 ? 16 : sk);
-      const int pslot = prof_begin(ctx, st, ctx->prof);
-      int used[2] = {5, 1};
-      const int rc = gemm_pp_kmajor(st, q, ctx->slab, ctx->slab_bytes, sk, used);
-      prof_end(ctx, st, pslot, used[0], used[1], 2.0 * R * d * (double)ctx->Vp);
-      if (rc != TST_OK && ctx->err.empty()) ctx->err = "gemm_pp_kmajor (NN, head) rc=" + std::to_string(rc);
-      CTX_RC(rc);
+      CTX_RC(run_gemm_kmajor(ctx, q, false, sk, 2.0 * R * d * (double)ctx->Vp, "NN, head"));
       dxf_done = true;
     }
   }
@@ -1211,58 +1308,17 @@ int backward(CtxT<AT>* ctx, int num_items) {
   for (int l = ctx->L - 1; l >= 0; --l) {
     LayerT<AT>& W = ctx->layers[l];
     if (lc && l == ctx->L - 1) {
-      // the compacted last layer (forward): dxg IS the gradient of its output rows; MLP and o projection backward on those R rows, then the rows
-      // go back to their token positions in front of the attention backward (zeros elsewhere: no other row of this layer's output is read)
-      ctx->lc_active = true;
-      int rc = linear_bwd<AT>(ctx, ctx->dxg, d, ctx->lc_act, ctx->F, W.Wd, W.WdT, W.g_d, ctx->lc_us_d, ctx->lc_dact, R, nullptr, 0);
-      bool du_done = false;
-      if (rc == TST_OK) {
-        SwiRank sr;
-        if (ctx->gpt2) rc = gelu_bwd<AT>(st, ctx->lc_dact, ctx->lc_gu, ctx->lc_dgu, (long)R * ctx->F);
-        else if (swr_setup<AT>(ctx, W.g_gu, true, R, du_target(ctx, W.g_gu, 1), sr)) {
-          if constexpr (sizeof(AT) == 2) rc = swiglu_rank_bwd(st, ctx->lc_dact, ctx->lc_gu, ctx->lc_dgu, R, ctx->F, sr);
-          du_done = true;
-        } else rc = swiglu_bwd<AT>(st, ctx->lc_dact, ctx->lc_gu, ctx->lc_dgu, R, ctx->F);
-      }
-      if (rc == TST_OK) rc = linear_bwd<AT>(ctx, ctx->lc_dgu, ctx->Fgu, ctx->lc_xn2, d, W.Wgu, W.WguT, W.g_gu, ctx->lc_us_gu, ctx->lc_dxn, R, nullptr, 1, true, du_done);
-      if (rc == TST_OK) rc = norm_bwd<AT>(ctx, ctx->lc_dxn, ctx->lc_hmid, ctx->lc_rstd2, W.mlp_norm, ctx->dxg, ctx->lc_dH, R);
-      if (rc == TST_OK) rc = linear_bwd<AT>(ctx, ctx->lc_dH, d, ctx->lc_attn, ctx->dattn, W.Wo, W.WoT, W.g_o, ctx->lc_us_o, ctx->lc_dattn, R, nullptr, 2);
-      if (rc == TST_OK) rc = flush_tn(ctx);   // these three groups contract over the compact rows: their own launch, with the rows' slot boundaries
-      ctx->lc_active = false;
-      CTX_RC(rc);
+      // the compacted last layer (forward): MLP and o projection backward on its R rows, then the rows go back to their token positions in front of the
+      // attention backward (zeros elsewhere: no other row of this layer's output is read)
+      const TailBufsT<AT> B = compact_tail(ctx);
+      CTX_RC(tail_bwd<AT>(ctx, W, compact_rows(ctx), B));
+      CTX_RC(flush_tn(ctx, compact_rows(ctx)));   // these three groups contract over the compact rows: their own launch, with the rows' slot boundaries
       CTX_HIP(hipMemsetAsync(ctx->dattn_b, 0, (size_t)T * ctx->dattn * sizeof(AT), st));
-      CTX_RC(gather_rows<AT>(st, ctx->lc_dattn, ctx->d_lab_idx, ctx->dattn_b, R, ctx->dattn, 1));
+      CTX_RC(gather_rows<AT>(st, B.dattn, ctx->d_lab_idx, ctx->dattn_b, R, ctx->dattn, 1));
       CTX_HIP(hipMemsetAsync(ctx->dH, 0, (size_t)T * d * sizeof(AT), st));
-      CTX_RC(gather_rows<AT>(st, ctx->lc_dH, ctx->d_lab_idx, ctx->dH, R, d, 1));
+      CTX_RC(gather_rows<AT>(st, B.dH, ctx->d_lab_idx, ctx->dH, R, d, 1));
     } else {
-    // MLP block: x_out = hmid + down(act)
-    if (full && W.bd) CTX_RC(colsum<AT>(st, ctx->dX, d, gof(W.bd), T, d, ctx->colred_ws));
-    CTX_RC(linear_bwd<AT>(ctx, ctx->dX, d, W.act, ctx->F, W.Wd, W.WdT, W.g_d, W.us_d, ctx->dact, T, gof(W.Wd), 0));
-    bool du_done = false;
-    if (ctx->gpt2) CTX_RC(gelu_bwd<AT>(st, ctx->dact, W.gu, ctx->dgu, (long)T * ctx->F));
-    else {
-      const int slot = prof_begin(ctx, st, ctx->prof_hbm);
-      SwiRank sr;
-      if (swr_setup<AT>(ctx, W.g_gu, true, T, du_target(ctx, W.g_gu, 1), sr)) {   // dgu AND the gate|up projection's du = dgu . Bg in one pass
-        if constexpr (sizeof(AT) == 2) CTX_RC(swiglu_rank_bwd(st, ctx->dact, W.gu, ctx->dgu, T, ctx->F, sr));
-        du_done = true;
-      } else if (!(whatif() & 4)) CTX_RC(swiglu_bwd<AT>(st, ctx->dact, W.gu, ctx->dgu, T, ctx->F));
-      prof_end(ctx, st, slot, PROF_SWIGLU, 1, 5.0 * T * ctx->F * sizeof(AT));   // read dact, gate, up; write dgate, dup
-    }
-    if (full && W.bgu) CTX_RC(colsum<AT>(st, ctx->dgu, ctx->Fgu, gof(W.bgu), T, ctx->Fgu, ctx->colred_ws));
-    CTX_RC(ndw_wait(ctx, 1));   // (the previous layer's attention-norm reduction on the side stream reads dxn, which the contraction below overwrites)
-    CTX_RC(linear_bwd<AT>(ctx, ctx->dgu, ctx->Fgu, W.xn2, d, W.Wgu, W.WguT, W.g_gu, W.us_gu, ctx->dxn, T, gof(W.Wgu), 1, true, du_done));
-    {
-      int frc = TST_OK;
-      if (!norm_bwd_dw<AT>(ctx, ctx->dxn, W.hmid, W.rstd2, W.mlp_norm, ctx->dX, ctx->dH, gof(W.mlp_norm), T, &frc)) {
-        if (full) CTX_RC(norm_dw<AT>(ctx, ctx->dxn, W.hmid, W.rstd2, gof(W.mlp_norm), gof(W.mlp_norm_b), T, 0));
-        CTX_RC(norm_bwd<AT>(ctx, ctx->dxn, W.hmid, W.rstd2, W.mlp_norm, ctx->dX, ctx->dH, T));
-      }
-      CTX_RC(frc);
-    }
-    // attention block: hmid = x_in + o(attn)
-    if (full && W.bo) CTX_RC(colsum<AT>(st, ctx->dH, d, gof(W.bo), T, d, ctx->colred_ws));
-    CTX_RC(linear_bwd<AT>(ctx, ctx->dH, d, W.attn, ctx->dattn, W.Wo, W.WoT, W.g_o, W.us_o, ctx->dattn_b, T, gof(W.Wo), 2));
+      CTX_RC(tail_bwd<AT>(ctx, W, rows, token_tail(ctx, W)));
     }
     const bool rope_in = !ctx->gpt2 && rope_fused(ctx);   // (the same answer as in this step's forward: same batch, process-wide switches)
     const bool attn_order = attn_order_on();
@@ -1286,8 +1342,8 @@ int backward(CtxT<AT>* ctx, int num_items) {
     const bool input_grad = full || l > 0;
     AT* dxq = ctx->dxn;
     CTX_RC(ndw_wait(ctx, 0));   // (this layer's MLP-norm reduction on the side stream reads dxn)
-    CTX_RC(linear_bwd<AT>(ctx, ctx->dqkv_b, ctx->dqkv, W.xn1, d, W.Wqkv, W.WqkvT, W.g_qkv, W.us_qkv, dxq, T, gof(W.Wqkv), 3, input_grad));
-    CTX_RC(flush_tn(ctx));
+    CTX_RC(linear_bwd<AT>(ctx, ctx->dqkv_b, W.xn1, W.proj[P_QKV], W.us_qkv, dxq, rows, gof(W.proj[P_QKV].W), 3, input_grad));
+    CTX_RC(flush_tn(ctx, rows));
     // (this layer's dy buffers (dX, dgu, dH, dqkv_b) and du4 are still intact here)
     if (!full && ctx->side && gemm_big_tile_level(-1) == 3) {
       // join: the side stream still reads this layer's dy buffers (dX, dgu, dH, dqkv_b) and du4; dX is overwritten next, the
@@ -1330,12 +1386,8 @@ int refresh_transposes(CtxT<AT>* ctx) {
   const int d = ctx->d;
   if (!ctx->lm_headT) return TST_OK;   // (ctx->kmajor bit 0: a full fine-tune that contracts dX against the stored weights keeps no W^T copies)
   CTX_RC(transpose_mat<AT>(st, ctx->lm_head, d, ctx->lm_headT, ctx->Vp, ctx->Vp, d, ctx->Vp));
-  for (auto& W : ctx->layers) {
-    CTX_RC(transpose_mat<AT>(st, W.Wqkv, d, W.WqkvT, ctx->dqkv, ctx->dqkv, d, ctx->dqkv));
-    CTX_RC(transpose_mat<AT>(st, W.Wo, ctx->dattn, W.WoT, d, d, ctx->dattn, d));
-    CTX_RC(transpose_mat<AT>(st, W.Wgu, d, W.WguT, ctx->Fgu, ctx->Fgu, d, ctx->Fgu));
-    CTX_RC(transpose_mat<AT>(st, W.Wd, ctx->F, W.WdT, d, d, ctx->F, d));
-  }
+  for (auto& W : ctx->layers)
+    for (const ProjT<AT>& P : W.proj) CTX_RC(transpose_mat<AT>(st, P.W, P.din, P.WT, P.dout, P.dout, P.din, P.dout));
   return TST_OK;
 }
 
@@ -1380,74 +1432,69 @@ int add_group(CtxT<AT>* ctx, int layer, LoraGroupT<AT>& g, int din, int dout, co
   return TST_OK;
 }
 
+// HF state_dict name -> its entry in the context's table (nullptr: the family has no such tensor)
 template <typename AT>
-struct WeightRefT {
-  AT* ptr = nullptr;
-  int64_t numel = 0;
-  int conv_in = 0, conv_out = 0;  // GPT-2 Conv1D weight: the HF tensor is [in, out]; the device tensor is [out, in]
-};
-
-// GPT-2 state_dict names (modeling_gpt2.py:486-497, 637-646)
-template <typename AT>
-WeightRefT<AT> find_weight_gpt2(CtxT<AT>* ctx, const char* name) {
-  WeightRefT<AT> r;
-  const int d = ctx->d, F = ctx->F;
-  std::string n(name);
-  if (n == "transformer.wte.weight" || n == "lm_head.weight") { r.ptr = ctx->embed; r.numel = (int64_t)ctx->V * d; return r; }  // tied (:638)
-  if (n == "transformer.wpe.weight") { r.ptr = ctx->wpe; r.numel = (int64_t)ctx->npos * d; return r; }
-  if (n == "transformer.ln_f.weight") { r.ptr = ctx->final_norm; r.numel = d; return r; }
-  if (n == "transformer.ln_f.bias") { r.ptr = ctx->final_norm_b; r.numel = d; return r; }
-  int l = -1;
-  char rest[128];
-  if (sscanf(name, "transformer.h.%d.%127s", &l, rest) != 2 || l < 0 || l >= ctx->L) return r;
-  LayerT<AT>& W = ctx->layers[l];
-  std::string s(rest);
-  auto conv = [&](AT* p, int in, int out) { r.ptr = p; r.numel = (int64_t)in * out; r.conv_in = in; r.conv_out = out; };
-  if (s == "ln_1.weight") { r.ptr = W.attn_norm; r.numel = d; }
-  else if (s == "ln_1.bias") { r.ptr = W.attn_norm_b; r.numel = d; }
-  else if (s == "ln_2.weight") { r.ptr = W.mlp_norm; r.numel = d; }
-  else if (s == "ln_2.bias") { r.ptr = W.mlp_norm_b; r.numel = d; }
-  else if (s == "attn.c_attn.weight") conv(W.Wqkv, d, 3 * d);
-  else if (s == "attn.c_attn.bias") { r.ptr = W.bqkv; r.numel = 3 * d; }
-  else if (s == "attn.c_proj.weight") conv(W.Wo, d, d);
-  else if (s == "attn.c_proj.bias") { r.ptr = W.bo; r.numel = d; }
-  else if (s == "mlp.c_fc.weight") conv(W.Wgu, d, F);
-  else if (s == "mlp.c_fc.bias") { r.ptr = W.bgu; r.numel = F; }
-  else if (s == "mlp.c_proj.weight") conv(W.Wd, F, d);
-  else if (s == "mlp.c_proj.bias") { r.ptr = W.bd; r.numel = d; }
-  return r;
+const typename CtxT<AT>::Named* find_weight(const CtxT<AT>* ctx, const char* name) {
+  for (const auto& t : ctx->named)
+    if (t.name == name) return &t;
+  return nullptr;
 }
 
-// HF state_dict name -> slice of the fused device tensors
+// The table's builders, one per naming scheme; every pointer is assigned by now. mat: [rows, cols] as stored; vec: [n] as 1 x n; optional tensors appear where they exist.
+// Llama / Qwen2 / Qwen3 (modeling_llama.py; q|k|v and gate|up are fused on the device: the HF tensors are row slices)
 template <typename AT>
-WeightRefT<AT> find_weight(CtxT<AT>* ctx, const char* name) {
-  if (ctx->gpt2) return find_weight_gpt2(ctx, name);
-  WeightRefT<AT> r;
+void name_tensors_llama(CtxT<AT>* ctx) {
+  const int d = ctx->d, F = ctx->F, dq = ctx->dq, dkv = ctx->dkv;
+  auto add = [&](const std::string& n, AT* p, int64_t rows, int64_t cols) { if (p) ctx->named.push_back({n, p, rows, cols, false, false}); };
+  add("model.embed_tokens.weight", ctx->embed, ctx->V, d);
+  add("lm_head.weight", ctx->lm_head, ctx->V, d);
+  add("model.norm.weight", ctx->final_norm, 1, d);
+  for (int l = 0; l < ctx->L; ++l) {
+    const LayerT<AT>& W = ctx->layers[l];
+    const std::string pre = "model.layers." + std::to_string(l) + ".";
+    AT *Wqkv = W.proj[P_QKV].W, *Wgu = W.proj[P_GU].W;
+    add(pre + "input_layernorm.weight", W.attn_norm, 1, d);
+    add(pre + "post_attention_layernorm.weight", W.mlp_norm, 1, d);
+    add(pre + "self_attn.q_proj.weight", Wqkv, dq, d);
+    add(pre + "self_attn.k_proj.weight", Wqkv + (int64_t)dq * d, dkv, d);
+    add(pre + "self_attn.v_proj.weight", Wqkv + (int64_t)(dq + dkv) * d, dkv, d);
+    add(pre + "self_attn.o_proj.weight", W.proj[P_O].W, d, ctx->dattn);
+    add(pre + "mlp.gate_proj.weight", Wgu, F, d);
+    add(pre + "mlp.up_proj.weight", Wgu + (int64_t)F * d, F, d);
+    add(pre + "mlp.down_proj.weight", W.proj[P_D].W, d, F);
+    if (W.bqkv) {   // Qwen2
+      add(pre + "self_attn.q_proj.bias", W.bqkv, 1, dq);
+      add(pre + "self_attn.k_proj.bias", W.bqkv + dq, 1, dkv);
+      add(pre + "self_attn.v_proj.bias", W.bqkv + dq + dkv, 1, dkv);
+    }
+    add(pre + "self_attn.q_norm.weight", W.q_norm, 1, ctx->dh);   // Qwen3
+    add(pre + "self_attn.k_norm.weight", W.k_norm, 1, ctx->dh);
+  }
+}
+// GPT-2 (modeling_gpt2.py:486-497, 637-646): Conv1D weights are [in, out] in HF and [out, in] on the device; the head is tied to wte (:638)
+template <typename AT>
+void name_tensors_gpt2(CtxT<AT>* ctx) {
   const int d = ctx->d;
-  std::string n(name);
-  if (n == "model.embed_tokens.weight") { r.ptr = ctx->embed; r.numel = (int64_t)ctx->V * d; return r; }
-  if (n == "lm_head.weight") { r.ptr = ctx->lm_head; r.numel = (int64_t)ctx->V * d; return r; }
-  if (n == "model.norm.weight") { r.ptr = ctx->final_norm; r.numel = d; return r; }
-  int l = -1;
-  char rest[128];
-  if (sscanf(name, "model.layers.%d.%127s", &l, rest) != 2 || l < 0 || l >= ctx->L) return r;
-  LayerT<AT>& W = ctx->layers[l];
-  std::string s(rest);
-  if (s == "input_layernorm.weight") { r.ptr = W.attn_norm; r.numel = d; }
-  else if (s == "post_attention_layernorm.weight") { r.ptr = W.mlp_norm; r.numel = d; }
-  else if (s == "self_attn.q_proj.weight") { r.ptr = W.Wqkv; r.numel = (int64_t)ctx->dq * d; }
-  else if (s == "self_attn.k_proj.weight") { r.ptr = W.Wqkv + (int64_t)ctx->dq * d; r.numel = (int64_t)ctx->dkv * d; }
-  else if (s == "self_attn.v_proj.weight") { r.ptr = W.Wqkv + (int64_t)(ctx->dq + ctx->dkv) * d; r.numel = (int64_t)ctx->dkv * d; }
-  else if (s == "self_attn.o_proj.weight") { r.ptr = W.Wo; r.numel = (int64_t)d * ctx->dattn; }
-  else if (W.q_norm && s == "self_attn.q_norm.weight") { r.ptr = W.q_norm; r.numel = ctx->dh; }
-  else if (W.k_norm && s == "self_attn.k_norm.weight") { r.ptr = W.k_norm; r.numel = ctx->dh; }
-  else if (W.bqkv && s == "self_attn.q_proj.bias") { r.ptr = W.bqkv; r.numel = ctx->dq; }
-  else if (W.bqkv && s == "self_attn.k_proj.bias") { r.ptr = W.bqkv + ctx->dq; r.numel = ctx->dkv; }
-  else if (W.bqkv && s == "self_attn.v_proj.bias") { r.ptr = W.bqkv + ctx->dq + ctx->dkv; r.numel = ctx->dkv; }
-  else if (s == "mlp.gate_proj.weight") { r.ptr = W.Wgu; r.numel = (int64_t)ctx->F * d; }
-  else if (s == "mlp.up_proj.weight") { r.ptr = W.Wgu + (int64_t)ctx->F * d; r.numel = (int64_t)ctx->F * d; }
-  else if (s == "mlp.down_proj.weight") { r.ptr = W.Wd; r.numel = (int64_t)d * ctx->F; }
-  return r;
+  auto add = [&](const std::string& n, AT* p, int64_t rows, int64_t cols, bool conv1d = false, bool alias = false) { ctx->named.push_back({n, p, rows, cols, conv1d, alias}); };
+  add("transformer.wte.weight", ctx->embed, ctx->V, d);
+  add("lm_head.weight", ctx->embed, ctx->V, d, false, true);
+  add("transformer.wpe.weight", ctx->wpe, ctx->npos, d);
+  add("transformer.ln_f.weight", ctx->final_norm, 1, d);
+  add("transformer.ln_f.bias", ctx->final_norm_b, 1, d);
+  static const char* const mod[4] = {"attn.c_attn", "attn.c_proj", "mlp.c_fc", "mlp.c_proj"};   // P_QKV .. P_D
+  for (int l = 0; l < ctx->L; ++l) {
+    const LayerT<AT>& W = ctx->layers[l];
+    const std::string pre = "transformer.h." + std::to_string(l) + ".";
+    AT* const bias[4] = {W.bqkv, W.bo, W.bgu, W.bd};
+    add(pre + "ln_1.weight", W.attn_norm, 1, d);
+    add(pre + "ln_1.bias", W.attn_norm_b, 1, d);
+    add(pre + "ln_2.weight", W.mlp_norm, 1, d);
+    add(pre + "ln_2.bias", W.mlp_norm_b, 1, d);
+    for (int p = 0; p < 4; ++p) {
+      add(pre + mod[p] + ".weight", W.proj[p].W, W.proj[p].dout, W.proj[p].din, true);
+      add(pre + mod[p] + ".bias", bias[p], 1, W.proj[p].dout);
+    }
+  }
 }
 
 template <typename AT>
@@ -1463,6 +1510,10 @@ int build_ctx(CtxT<AT>* ctx) {
   ctx->dq = ctx->H * ctx->dh; ctx->dkv = ctx->Hkv * ctx->dh; ctx->dqkv = ctx->dq + 2 * ctx->dkv; ctx->dattn = ctx->dq;
   ctx->Tmax = c.max_tokens; ctx->Smax = c.max_seqs; ctx->Rmax = c.max_labelled;
   ctx->Tpad_max = roundup(ctx->Tmax, 64);
+  {   // a layer's four projections [dout, din]: q|k|v, o, gate|up (GPT-2: c_fc), down
+    const int pd[4][2] = {{ctx->dqkv, ctx->d}, {ctx->d, ctx->dattn}, {ctx->Fgu, ctx->d}, {ctx->d, ctx->F}};
+    for (int p = 0; p < 4; ++p) { ctx->proj_dout[p] = pd[p][0]; ctx->proj_din[p] = pd[p][1]; }
+  }
   // every [tokens, .] buffer has Tpad_max rows: the TN contractions read whole 64-row k-steps (rows >= n_tokens are
   // masked in-kernel but must be readable and finite, hence the zero fill below)
   const int d = ctx->d, F = ctx->F, V = ctx->Vp, L = ctx->L, T = ctx->Tpad_max, Tp = ctx->Tpad_max, Fgu = ctx->Fgu;
@@ -1514,11 +1565,8 @@ int build_ctx(CtxT<AT>* ctx) {
   // full fine-tune: one flat bf16 buffer in the master's order: [embed | per layer Wqkv, Wo, Wgu, Wd | lm_head | norms]
   int64_t wofs = 0;
   auto take = [&](int64_t n) { AT* p = ctx->wb + wofs; wofs += n; return p; };
-  auto reg = [&](const std::string& name, const AT* p, int64_t rows, int64_t cols) {
-    ctx->tinfo.push_back({name, (int64_t)(p - ctx->wb), rows, cols});
-  };
   if (ctx->full) {
-    const int64_t per_layer = (int64_t)ctx->dqkv * d + (int64_t)d * ctx->dattn + (int64_t)Fgu * d + (int64_t)d * F;
+    const int64_t per_layer = layer_numel(ctx);
     // GPT-2: one tied [V, d] matrix + wpe; per layer 2 LayerNorms with bias and 4 Conv1D biases, + ln_f
     ctx->n_decay = (gpt2 ? (int64_t)V * d + (int64_t)ctx->npos * d : 2 * (int64_t)V * d) + L * per_layer;
     ctx->n_train = ctx->n_decay + (gpt2 ? (int64_t)L * (4 * d + ctx->dqkv + d + Fgu + d) + 2 * d
@@ -1532,11 +1580,7 @@ int build_ctx(CtxT<AT>* ctx) {
     ALLOC(ctx->wb, AT, ctx->n_pad);     // (all-gather target: zero_ranks equal shards)
     ALLOC(ctx->wb0, AT, ctx->n_train);
     ctx->embed = take((int64_t)V * d);
-    reg(gpt2 ? "transformer.wte.weight" : "model.embed_tokens.weight", ctx->embed, ctx->V, d);
-    if (gpt2) {
-      ctx->wpe = take((int64_t)ctx->npos * d);
-      reg("transformer.wpe.weight", ctx->wpe, ctx->npos, d);
-    }
+    if (gpt2) ctx->wpe = take((int64_t)ctx->npos * d);
     if (!(ctx->kmajor & 1)) ALLOC(ctx->lm_headT, AT, (int64_t)V * d);
   } else if (sh) {
     ctx->embed = sh->embed; ctx->lm_head = sh->lm_head; ctx->lm_headT = sh->lm_headT; ctx->final_norm = sh->final_norm;
@@ -1564,36 +1608,19 @@ int build_ctx(CtxT<AT>* ctx) {
   static const char* g_d[1] = {"mlp.c_proj"};
   for (int l = 0; l < L; ++l) {
     LayerT<AT>& W = ctx->layers[l];
+    const LoraGroupT<AT>* const groups[4] = {&W.g_qkv, &W.g_o, &W.g_gu, &W.g_d};
+    for (int p = 0; p < 4; ++p) { W.proj[p].dout = ctx->proj_dout[p]; W.proj[p].din = ctx->proj_din[p]; W.proj[p].g = groups[p]; }
     if (ctx->full) {
-      const std::string pre = (gpt2 ? "transformer.h." : "model.layers.") + std::to_string(l) + ".";
-      W.Wqkv = take((int64_t)ctx->dqkv * d);
-      W.Wo = take((int64_t)d * ctx->dattn);
-      W.Wgu = take((int64_t)Fgu * d);
-      W.Wd = take((int64_t)d * F);
-      if (gpt2) {  // rows/cols describe the device layout [out, in] (the HF Conv1D tensor is its transpose)
-        reg(pre + "attn.c_attn.weight", W.Wqkv, ctx->dqkv, d);
-        reg(pre + "attn.c_proj.weight", W.Wo, d, ctx->dattn);
-        reg(pre + "mlp.c_fc.weight", W.Wgu, F, d);
-        reg(pre + "mlp.c_proj.weight", W.Wd, d, F);
-      } else {
-        reg(pre + "self_attn.q_proj.weight", W.Wqkv, ctx->dq, d);
-        reg(pre + "self_attn.k_proj.weight", W.Wqkv + (int64_t)ctx->dq * d, ctx->dkv, d);
-        reg(pre + "self_attn.v_proj.weight", W.Wqkv + (int64_t)(ctx->dq + ctx->dkv) * d, ctx->dkv, d);
-        reg(pre + "self_attn.o_proj.weight", W.Wo, d, ctx->dattn);
-        reg(pre + "mlp.gate_proj.weight", W.Wgu, F, d);
-        reg(pre + "mlp.up_proj.weight", W.Wgu + (int64_t)F * d, F, d);
-        reg(pre + "mlp.down_proj.weight", W.Wd, d, F);
-      }
-      if (!(ctx->kmajor & 1)) {   // (else dX = dY . W on the NN member: one copy of every weight)
-        ALLOC(W.WqkvT, AT, (int64_t)ctx->dqkv * d); ALLOC(W.WoT, AT, (int64_t)d * ctx->dattn);
-        ALLOC(W.WguT, AT, (int64_t)Fgu * d); ALLOC(W.WdT, AT, (int64_t)d * F);
+      for (auto& P : W.proj) {
+        P.W = take(P.numel());
+        if (!(ctx->kmajor & 1)) ALLOC(P.WT, AT, P.numel());   // (else dX = dY . W on the NN member: one copy of every weight)
       }
     } else if (sh) {
       const LayerT<AT>& S = sh->layers[l];
       W.attn_norm = S.attn_norm; W.mlp_norm = S.mlp_norm; W.bqkv = S.bqkv;
       W.q_norm = S.q_norm; W.k_norm = S.k_norm;
       W.attn_norm_b = S.attn_norm_b; W.mlp_norm_b = S.mlp_norm_b; W.bo = S.bo; W.bgu = S.bgu; W.bd = S.bd;
-      W.Wqkv = S.Wqkv; W.WqkvT = S.WqkvT; W.Wo = S.Wo; W.WoT = S.WoT; W.Wgu = S.Wgu; W.WguT = S.WguT; W.Wd = S.Wd; W.WdT = S.WdT;
+      for (int p = 0; p < 4; ++p) { W.proj[p].W = S.proj[p].W; W.proj[p].WT = S.proj[p].WT; }
     } else {
       ALLOC(W.attn_norm, AT, d); ALLOC(W.mlp_norm, AT, d);
       if (qkv_bias) ALLOC(W.bqkv, AT, ctx->dqkv);
@@ -1602,10 +1629,7 @@ int build_ctx(CtxT<AT>* ctx) {
         ALLOC(W.attn_norm_b, AT, d); ALLOC(W.mlp_norm_b, AT, d);
         ALLOC(W.bo, AT, d); ALLOC(W.bgu, AT, Fgu); ALLOC(W.bd, AT, d);
       }
-      ALLOC(W.Wqkv, AT, (int64_t)ctx->dqkv * d); ALLOC(W.WqkvT, AT, (int64_t)ctx->dqkv * d);
-      ALLOC(W.Wo, AT, (int64_t)d * ctx->dattn); ALLOC(W.WoT, AT, (int64_t)d * ctx->dattn);
-      ALLOC(W.Wgu, AT, (int64_t)Fgu * d); ALLOC(W.WguT, AT, (int64_t)Fgu * d);
-      ALLOC(W.Wd, AT, (int64_t)d * F); ALLOC(W.WdT, AT, (int64_t)d * F);
+      for (auto& P : W.proj) { ALLOC(P.W, AT, P.numel()); ALLOC(P.WT, AT, P.numel()); }
     }
     const unsigned t = ctx->full ? 0u : c.lora_targets;
     if (gpt2) {
@@ -1645,55 +1669,28 @@ int build_ctx(CtxT<AT>* ctx) {
   }
   ALLOC(ctx->x_last, AT, (int64_t)T * d);
   if (ctx->full) {
-    if (gpt2) {
-      ctx->lm_head = ctx->embed;  // tied head: one parameter, its gradient is the sum of both uses
-    } else {
-      ctx->lm_head = take((int64_t)V * d);
-      reg("lm_head.weight", ctx->lm_head, ctx->V, d);
-    }
-    for (int l = 0; l < L && gpt2; ++l) {
-      const std::string pre = "transformer.h." + std::to_string(l) + ".";
-      LayerT<AT>& W = ctx->layers[l];
-      W.attn_norm = take(d); reg(pre + "ln_1.weight", W.attn_norm, 1, d);
-      W.attn_norm_b = take(d); reg(pre + "ln_1.bias", W.attn_norm_b, 1, d);
-      W.mlp_norm = take(d); reg(pre + "ln_2.weight", W.mlp_norm, 1, d);
-      W.mlp_norm_b = take(d); reg(pre + "ln_2.bias", W.mlp_norm_b, 1, d);
-      W.bqkv = take(ctx->dqkv); reg(pre + "attn.c_attn.bias", W.bqkv, 1, ctx->dqkv);
-      W.bo = take(d); reg(pre + "attn.c_proj.bias", W.bo, 1, d);
-      W.bgu = take(Fgu); reg(pre + "mlp.c_fc.bias", W.bgu, 1, Fgu);
-      W.bd = take(d); reg(pre + "mlp.c_proj.bias", W.bd, 1, d);
-    }
-    for (int l = 0; l < L && !gpt2; ++l) {
-      const std::string pre = "model.layers." + std::to_string(l) + ".";
-      ctx->layers[l].attn_norm = take(d);
-      reg(pre + "input_layernorm.weight", ctx->layers[l].attn_norm, 1, d);
-      ctx->layers[l].mlp_norm = take(d);
-      reg(pre + "post_attention_layernorm.weight", ctx->layers[l].mlp_norm, 1, d);
-      if (qkv_bias) {
-        AT* b = take(ctx->dqkv);
-        ctx->layers[l].bqkv = b;
-        reg(pre + "self_attn.q_proj.bias", b, 1, ctx->dq);
-        reg(pre + "self_attn.k_proj.bias", b + ctx->dq, 1, ctx->dkv);
-        reg(pre + "self_attn.v_proj.bias", b + ctx->dq + ctx->dkv, 1, ctx->dkv);
+    if (gpt2) ctx->lm_head = ctx->embed;  // tied head: one parameter, its gradient is the sum of both uses
+    else ctx->lm_head = take((int64_t)V * d);
+    // the no-decay tail, layer by layer: norm vectors and biases
+    for (auto& W : ctx->layers) {
+      if (gpt2) {
+        W.attn_norm = take(d); W.attn_norm_b = take(d); W.mlp_norm = take(d); W.mlp_norm_b = take(d);
+        W.bqkv = take(ctx->dqkv); W.bo = take(d); W.bgu = take(Fgu); W.bd = take(d);
+        continue;
       }
-      if (qk_norm) {   // Qwen3 head-norm vectors: with the other norm vectors in the no-decay tail (HF's Trainer excludes every "_norm" parameter from decay)
-        ctx->layers[l].q_norm = take(ctx->dh);
-        reg(pre + "self_attn.q_norm.weight", ctx->layers[l].q_norm, 1, ctx->dh);
-        ctx->layers[l].k_norm = take(ctx->dh);
-        reg(pre + "self_attn.k_norm.weight", ctx->layers[l].k_norm, 1, ctx->dh);
-      }
+      W.attn_norm = take(d);
+      W.mlp_norm = take(d);
+      if (qkv_bias) W.bqkv = take(ctx->dqkv);
+      // Qwen3 head-norm vectors: with the other norm vectors in the no-decay tail (HF's Trainer excludes every "_norm" parameter from decay)
+      if (qk_norm) { W.q_norm = take(ctx->dh); W.k_norm = take(ctx->dh); }
     }
     ctx->final_norm = take(d);
-    reg(gpt2 ? "transformer.ln_f.weight" : "model.norm.weight", ctx->final_norm, 1, d);
-    if (gpt2) {
-      ctx->final_norm_b = take(d);
-      reg("transformer.ln_f.bias", ctx->final_norm_b, 1, d);
-    }
+    if (gpt2) ctx->final_norm_b = take(d);
     if (wofs != ctx->n_train) return fail(ctx, TST_ESTATE, "internal: full fine-tune weight layout mismatch");
     {   // the allocation order above IS the flat layout; host_logic.h states the same layout as arithmetic (the CPU tests and the region table use it)
       const tsthost::FullLayout fl = tsthost::full_layout(tsthost::model_dims(c));
-      if (fl.n_train != ctx->n_train || fl.n_decay != ctx->n_decay || fl.embed != ctx->embed - ctx->wb || fl.layer0 != ctx->layers[0].Wqkv - ctx->wb ||
-          fl.lm_head != ctx->lm_head - ctx->wb || (gpt2 && fl.wpe != ctx->wpe - ctx->wb) || fl.tail != (gpt2 ? ctx->layers[0].attn_norm : ctx->layers[0].attn_norm) - ctx->wb)
+      if (fl.n_train != ctx->n_train || fl.n_decay != ctx->n_decay || fl.embed != ctx->embed - ctx->wb || fl.layer0 != ctx->layers[0].proj[P_QKV].W - ctx->wb ||
+          fl.lm_head != ctx->lm_head - ctx->wb || (gpt2 && fl.wpe != ctx->wpe - ctx->wb) || fl.tail != ctx->layers[0].attn_norm - ctx->wb)
         return fail(ctx, TST_ESTATE, "internal: full fine-tune layout disagrees with host_logic.h full_layout");
     }
   }
@@ -1738,7 +1735,7 @@ int build_ctx(CtxT<AT>* ctx) {
     CTX_HIP(hipMemcpy(ctx->sinT, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
   }
   // batch buffers
-  const size_t stage_ints = tsthost::stage_ints({ctx->Tmax, ctx->Smax, ctx->Rmax, ctx->V, c.max_position, ctx->ns});   // layout of upload_batch's staging buffer
+  const size_t stage_ints = tsthost::stage_ints(batch_limits(ctx));   // layout of upload_batch's staging buffer
   ALLOC(ctx->d_ids, int, stage_ints + 64);
   ctx->d_pos = ctx->d_ids + ctx->Tmax; ctx->d_cu = ctx->d_pos + ctx->Tmax; ctx->d_lab_idx = ctx->d_cu + (ctx->Smax + 1); ctx->d_targets = ctx->d_lab_idx + ctx->Rmax; ctx->d_order = ctx->d_targets + ctx->Rmax;
   ALLOC(ctx->d_opt_ids, int, 256);
@@ -1790,9 +1787,7 @@ int build_ctx(CtxT<AT>* ctx) {
   if (ctx->full) {
     // gradient regions in the order backward finishes them: lm_head (untied), layers L-1 .. 0, embedding side, norm / bias tail (host_logic.h)
     ctx->gn_regions = tsthost::full_layout(tsthost::model_dims(c)).regions;
-    for (int l = 0; l < L; ++l)
-      ctx->gn_cap += (int64_t)tst_ceil_div(ctx->dqkv, 256) * tst_ceil_div(d, 256) + (int64_t)tst_ceil_div(d, 256) * tst_ceil_div(ctx->dattn, 256) +
-                     (int64_t)tst_ceil_div(Fgu, 256) * tst_ceil_div(d, 256) + (int64_t)tst_ceil_div(d, 256) * tst_ceil_div(F, 256) + 4 * 2048;
+    for (int p = 0; p < 4; ++p) ctx->gn_cap += L * gn_slots(ctx->proj_dout[p], ctx->proj_din[p]);
     ctx->gn_cap += 3 * 1024;   // embedding side, head, norm / bias tail: summed at the optimizer step
     ALLOC(ctx->gn_partial, float, ctx->gn_cap);
   }
@@ -1875,6 +1870,14 @@ int build_ctx(CtxT<AT>* ctx) {
     }
   }
 #undef ALLOC
+  if (gpt2) name_tensors_gpt2(ctx);
+  else name_tensors_llama(ctx);
+  if (ctx->full) {
+    // the trainables of a full fine-tune: the named tensors inside the flat buffer, in its order (tinfo is empty so far: no module group exists)
+    for (const auto& t : ctx->named)
+      if (!t.alias && t.ptr >= ctx->wb && t.ptr < ctx->wb + ctx->n_train) ctx->tinfo.push_back({t.name, (int64_t)(t.ptr - ctx->wb), t.rows, t.cols});
+    std::sort(ctx->tinfo.begin(), ctx->tinfo.end(), [](const TrainableInfo& a, const TrainableInfo& b) { return a.offset < b.offset; });
+  }
   CTX_HIP(hipMemcpy(ctx->descs_dev, ctx->descs.data(), ctx->descs.size() * sizeof(LoraGroupDescT<AT>), hipMemcpyHostToDevice));
   CTX_HIP(hipDeviceSynchronize());  // the ctx stream is non-blocking: setup copies/memsets must have landed before it is used
   return TST_OK;
@@ -1919,9 +1922,10 @@ int fork_impl(CtxT<AT>* parent, tst_ctx** out) {
 template <typename AT>
 int set_weight_impl(CtxT<AT>* ctx, const char* name, const void* host, int dtype, int64_t numel) {
   if (ctx->parent) return fail(ctx, TST_ESTATE, "a forked context borrows its parent's weights");
-  WeightRefT<AT> w = find_weight(ctx, name);
-  if (!w.ptr) return fail(ctx, TST_ENOTFOUND, std::string("unknown weight: ") + name);
-  if (w.numel != numel) return fail(ctx, TST_EINVAL, std::string("numel mismatch for ") + name);
+  const auto* t = find_weight(ctx, name);
+  if (!t) return fail(ctx, TST_ENOTFOUND, std::string("unknown weight: ") + name);
+  if (t->rows * t->cols != numel) return fail(ctx, TST_EINVAL, std::string("numel mismatch for ") + name);
+  const int64_t conv_in = t->conv1d ? t->cols : 0, conv_out = t->conv1d ? t->rows : 0;   // Conv1D: the HF tensor is [in, out], the device tensor [out, in]
   ctx->finalized = false;
   if (dtype != TST_DTYPE_BF16 && dtype != TST_DTYPE_F32) return fail(ctx, TST_EINVAL, "dtype must be TST_DTYPE_F32 or TST_DTYPE_BF16");
   const float* f = (const float*)host;
@@ -1929,7 +1933,7 @@ int set_weight_impl(CtxT<AT>* ctx, const char* name, const void* host, int dtype
   const bool same = (sizeof(AT) == 2) == (dtype == TST_DTYPE_BF16);
   std::vector<AT> tmp;
   const void* src = host;
-  if (!same || w.conv_in) {
+  if (!same || conv_in) {
     tmp.resize((size_t)numel);
     auto conv = [&](int64_t sidx) -> AT {
       if (sizeof(AT) == 2) return (AT)(dtype == TST_DTYPE_F32 ? host_f2bf(f[sidx]) : h[sidx]);
@@ -1938,38 +1942,39 @@ int set_weight_impl(CtxT<AT>* ctx, const char* name, const void* host, int dtype
       memcpy(&o, &v, sizeof(AT) < sizeof(v) ? sizeof(AT) : sizeof(v));
       return o;
     };
-    if (w.conv_in) {
-      for (int64_t i = 0; i < w.conv_in; ++i)
-        for (int64_t o = 0; o < w.conv_out; ++o) tmp[(size_t)(o * w.conv_in + i)] = conv(i * w.conv_out + o);
+    if (conv_in) {
+      for (int64_t i = 0; i < conv_in; ++i)
+        for (int64_t o = 0; o < conv_out; ++o) tmp[(size_t)(o * conv_in + i)] = conv(i * conv_out + o);
     } else {
       for (int64_t i = 0; i < numel; ++i) tmp[(size_t)i] = conv(i);
     }
     src = tmp.data();
   }
-  CTX_HIP(hipMemcpy(w.ptr, src, (size_t)numel * sizeof(AT), hipMemcpyHostToDevice));
+  CTX_HIP(hipMemcpy(t->ptr, src, (size_t)numel * sizeof(AT), hipMemcpyHostToDevice));
   if (ctx->qk_norm)
     for (auto& W : ctx->layers) {
-      if (w.ptr == W.q_norm) W.q_norm_set = true;
-      if (w.ptr == W.k_norm) W.k_norm_set = true;
+      if (t->ptr == W.q_norm) W.q_norm_set = true;
+      if (t->ptr == W.k_norm) W.k_norm_set = true;
     }
   return TST_OK;
 }
 
 template <typename AT>
 int get_weight_impl(CtxT<AT>* ctx, const char* name, float* host_out, int64_t numel) {
-  WeightRefT<AT> w = find_weight(ctx, name);
-  if (!w.ptr) return fail(ctx, TST_ENOTFOUND, std::string("unknown weight: ") + name);
-  if (w.numel != numel) return fail(ctx, TST_EINVAL, std::string("numel mismatch for ") + name);
+  const auto* t = find_weight(ctx, name);
+  if (!t) return fail(ctx, TST_ENOTFOUND, std::string("unknown weight: ") + name);
+  if (t->rows * t->cols != numel) return fail(ctx, TST_EINVAL, std::string("numel mismatch for ") + name);
+  const int64_t conv_in = t->conv1d ? t->cols : 0, conv_out = t->conv1d ? t->rows : 0;   // Conv1D: the HF tensor is [in, out], the device tensor [out, in]
   std::vector<AT> tmp((size_t)numel);
   CTX_RC(ctx_sync(ctx));
-  CTX_HIP(hipMemcpy(tmp.data(), w.ptr, (size_t)numel * sizeof(AT), hipMemcpyDeviceToHost));
+  CTX_HIP(hipMemcpy(tmp.data(), t->ptr, (size_t)numel * sizeof(AT), hipMemcpyDeviceToHost));
   auto val = [&](int64_t i) -> float {
     if (sizeof(AT) == 2) { uint16_t b; memcpy(&b, &tmp[(size_t)i], 2); return host_bf2f(b); }
     float v; memcpy(&v, &tmp[(size_t)i], sizeof(AT) < 4 ? sizeof(AT) : 4); return v;
   };
-  if (w.conv_in) {  // back to the HF Conv1D layout [in, out]
-    for (int64_t o = 0; o < w.conv_out; ++o)
-      for (int64_t i = 0; i < w.conv_in; ++i) host_out[i * w.conv_out + o] = val(o * w.conv_in + i);
+  if (conv_in) {  // back to the HF Conv1D layout [in, out]
+    for (int64_t o = 0; o < conv_out; ++o)
+      for (int64_t i = 0; i < conv_in; ++i) host_out[i * conv_out + o] = val(o * conv_in + i);
     return TST_OK;
   }
   for (int64_t i = 0; i < numel; ++i) host_out[i] = val(i);
@@ -2024,10 +2029,7 @@ int init_random_impl(CtxT<AT>* ctx, uint64_t seed, float stdv) {
       CTX_RC(fill_const<AT>(st, W.attn_norm_b, d, 0.0f)); CTX_RC(fill_const<AT>(st, W.mlp_norm_b, d, 0.0f));
       CTX_RC(fill_const<AT>(st, W.bo, d, 0.0f)); CTX_RC(fill_const<AT>(st, W.bgu, ctx->Fgu, 0.0f)); CTX_RC(fill_const<AT>(st, W.bd, d, 0.0f));
     }
-    CTX_RC(randn_fill<AT>(st, W.Wqkv, (long)ctx->dqkv * d, s += 101, stdv));
-    CTX_RC(randn_fill<AT>(st, W.Wo, (long)d * ctx->dattn, s += 101, stdv));
-    CTX_RC(randn_fill<AT>(st, W.Wgu, (long)ctx->Fgu * d, s += 101, stdv));
-    CTX_RC(randn_fill<AT>(st, W.Wd, (long)d * ctx->F, s += 101, stdv));
+    for (const ProjT<AT>& P : W.proj) CTX_RC(randn_fill<AT>(st, P.W, (long)P.numel(), s += 101, stdv));
   }
   ctx->finalized = false;
   return finalize_weights_impl(ctx);
@@ -2105,31 +2107,27 @@ int fwd_bwd_enqueue(CtxT<AT>* ctx, const tst_batch* b, int32_t num_items, const 
   CTX_RC(upload_batch(ctx, b, true, nullptr, 0));
   if (ctx->cur_R <= 0) return fail(ctx, TST_EINVAL, "batch has no labelled tokens");
   if (ctx->ns > 1 && num_items > 0) return fail(ctx, TST_EINVAL, "stacked folds: num_items must be 0 (every slot is normalised by its own labelled-token count, or by slot_items)");
-  ctx->items_override_on = false;
   for (int sl = 0; sl < ctx->ns; ++sl) ctx->slot_steps[sl] = ctx->ns == 1 ? true : (ctx->slot_r0[sl + 1] - ctx->slot_r0[sl] > 0);
   if (slot_items) {
     for (int sl = 0; sl < ctx->ns; ++sl) {
       const int rows = ctx->ns == 1 ? ctx->cur_R : ctx->slot_r0[sl + 1] - ctx->slot_r0[sl];
       if (rows > 0 && slot_items[sl] < rows) return fail(ctx, TST_EINVAL, "num_items of a slot is smaller than its labelled tokens in this batch");
-      ctx->items_override[sl] = slot_items[sl];
     }
-    ctx->items_override_on = true;
     if (ctx->ns == 1) num_items = slot_items[0];
   }
   const int items = num_items > 0 ? num_items : ctx->cur_R;
   ctx->cur_items = items;
   CTX_RC(forward(ctx, true));
   CTX_RC(head_forward(ctx, true));
-  const int rc = backward(ctx, items);
-  ctx->items_override_on = false;
-  return rc;
+  return backward(ctx, items, slot_items);
 }
 
 // workgroups (= partial sums, fixed assignment: reproducible) of the gradient-norm pass: 256 pulled the 168 MB of one Llama-3-8B adapter set at 1.1 TB/s
 inline int clip_parts(int64_t n) { return n > (64L << 20) ? 4096 : (n > (4L << 20) ? 1024 : 256); }
 
+// the optimizer steps take the gradient they apply as `tg`: the context's flat gradient, or the running sum of an accumulation window (tacc)
 template <typename AT>
-int opt_enqueue_stacked(CtxT<AT>* ctx, const float* lrs) {
+int opt_enqueue_stacked(CtxT<AT>* ctx, const float* lrs, float* tg) {
   const tst_model_cfg& c = ctx->cfg;
   hipStream_t st = ctx->stream;
   for (int sl = 0; sl < ctx->ns; ++sl) {
@@ -2138,9 +2136,9 @@ int opt_enqueue_stacked(CtxT<AT>* ctx, const float* lrs) {
     const double bc1 = 1.0 - pow((double)c.adam_beta1, (double)ctx->opt_steps[sl]);
     const double bc2 = 1.0 - pow((double)c.adam_beta2, (double)ctx->opt_steps[sl]);
     const int64_t o = sl * ctx->n1;
-    CTX_RC(grad_clip_coef(st, ctx->tg + o, ctx->n1, c.max_grad_norm, ctx->clip_partial, clip_parts(ctx->n1), ctx->clip_out + 2 * sl));
+    CTX_RC(grad_clip_coef(st, tg + o, ctx->n1, c.max_grad_norm, ctx->clip_partial, clip_parts(ctx->n1), ctx->clip_out + 2 * sl));
     const int slot = prof_begin(ctx, st, ctx->prof_hbm);
-    CTX_RC(adamw_step<AT>(st, ctx->tp + o, ctx->tg + o, ctx->tm + o, ctx->tv + o, ctx->n1, ctx->clip_out + 2 * sl, lrs[sl], c.adam_beta1, c.adam_beta2, c.adam_eps,
+    CTX_RC(adamw_step<AT>(st, ctx->tp + o, tg + o, ctx->tm + o, ctx->tv + o, ctx->n1, ctx->clip_out + 2 * sl, lrs[sl], c.adam_beta1, c.adam_beta2, c.adam_eps,
                       c.weight_decay, (float)bc1, (float)sqrt(bc2), nullptr));
     prof_end(ctx, st, slot, PROF_ADAMW, 1, 28.0 * ctx->n1);   // read p, g, m, v; write p, m, v (fp32)
   }
@@ -2165,7 +2163,7 @@ int get_trainable_sharded(CtxT<AT>* ctx, float* host_out) {
 // compute copy. Without a communicator (one-GPU shard tests) the collectives are skipped: the local gradient is the group sum, the norm is
 // taken over all of it, only this rank's shard of the weights moves.
 template <typename AT>
-int opt_enqueue_zero(CtxT<AT>* ctx, float lr) {
+int opt_enqueue_zero(CtxT<AT>* ctx, float lr, float* tg) {
   const tst_model_cfg& c = ctx->cfg;
   hipStream_t st = ctx->stream;
   ctx->opt_steps[0] += 1;
@@ -2176,14 +2174,14 @@ int opt_enqueue_zero(CtxT<AT>* ctx, float lr) {
   if (ctx->dp_comm) {
     if (ctx->dp_ranks != ctx->zero) return fail(ctx, TST_ESTATE, "the data-parallel group must have zero_ranks ranks");
     ctx->dp_n_coll += 1; ctx->dp_n_elems += ctx->n_pad;
-    if (ncclReduceScatter(ctx->tg, ctx->tg + (int64_t)ctx->zero_rank * ctx->z_shard, (size_t)ctx->z_shard, ncclFloat, ncclSum, ctx->dp_comm, st) != ncclSuccess)
+    if (ncclReduceScatter(tg, tg + (int64_t)ctx->zero_rank * ctx->z_shard, (size_t)ctx->z_shard, ncclFloat, ncclSum, ctx->dp_comm, st) != ncclSuccess)
       return fail(ctx, TST_EHIP, "ncclReduceScatter failed");
-    CTX_RC(sumsq_partial(st, ctx->tg + lo, nsh > 0 ? nsh : 1, ctx->clip_partial, 256));
+    CTX_RC(sumsq_partial(st, tg + lo, nsh > 0 ? nsh : 1, ctx->clip_partial, 256));
     CTX_RC(sum_partials(st, ctx->clip_partial, 256, ctx->z_sumsq));
     CTX_RC(dp_allreduce(ctx, ctx->z_sumsq, 1, st));
     CTX_RC(clip_from_sumsq(st, ctx->z_sumsq, c.max_grad_norm, ctx->clip_out));
   } else {
-    CTX_RC(grad_clip_coef(st, ctx->tg, ctx->n_train, c.max_grad_norm, ctx->clip_partial, clip_parts(ctx->n_train), ctx->clip_out));
+    CTX_RC(grad_clip_coef(st, tg, ctx->n_train, c.max_grad_norm, ctx->clip_partial, clip_parts(ctx->n_train), ctx->clip_out));
   }
   // HF's two parameter groups (trainer.py:1181-1196): decay on [0, n_decay), none on the norm / bias tail; the shard may straddle the border
   const float b1 = (float)bc1, b2s = (float)sqrt(bc2);
@@ -2191,10 +2189,10 @@ int opt_enqueue_zero(CtxT<AT>* ctx, float lr) {
   const tsthost::DecaySplit ds = tsthost::decay_split(lo, hi, ctx->n_decay);
   const int64_t d_hi = ds.d_hi;
   if (d_hi > lo)
-    CTX_RC(adamw_step<AT>(st, ctx->tp, ctx->tg + lo, ctx->tm, ctx->tv, d_hi - lo, ctx->clip_out, lr, c.adam_beta1, c.adam_beta2, c.adam_eps, c.weight_decay, b1, b2s, ctx->wb + lo));
+    CTX_RC(adamw_step<AT>(st, ctx->tp, tg + lo, ctx->tm, ctx->tv, d_hi - lo, ctx->clip_out, lr, c.adam_beta1, c.adam_beta2, c.adam_eps, c.weight_decay, b1, b2s, ctx->wb + lo));
   const int64_t n_lo = ds.n_lo;
   if (hi > n_lo)
-    CTX_RC(adamw_step<AT>(st, ctx->tp + (n_lo - lo), ctx->tg + n_lo, ctx->tm + (n_lo - lo), ctx->tv + (n_lo - lo), hi - n_lo, ctx->clip_out, lr, c.adam_beta1, c.adam_beta2,
+    CTX_RC(adamw_step<AT>(st, ctx->tp + (n_lo - lo), tg + n_lo, ctx->tm + (n_lo - lo), ctx->tv + (n_lo - lo), hi - n_lo, ctx->clip_out, lr, c.adam_beta1, c.adam_beta2,
                           c.adam_eps, 0.0f, b1, b2s, ctx->wb + n_lo));
   prof_end(ctx, st, slot, PROF_ADAMW, 1, (28.0 + sizeof(AT)) * nsh);
   if (ctx->dp_comm) {
@@ -2206,8 +2204,8 @@ int opt_enqueue_zero(CtxT<AT>* ctx, float lr) {
 }
 
 template <typename AT>
-int opt_enqueue(CtxT<AT>* ctx, float lr) {
-  if (ctx->zero_on) return opt_enqueue_zero(ctx, lr);
+int opt_enqueue(CtxT<AT>* ctx, float lr, float* tg) {
+  if (ctx->zero_on) return opt_enqueue_zero(ctx, lr, tg);
   const tst_model_cfg& c = ctx->cfg;
   hipStream_t st = ctx->stream;
   // a pending overlapped step still reads clip_out and the gradient-norm partials that this call rewrites on the context's stream (two optimizer steps with no
@@ -2216,7 +2214,7 @@ int opt_enqueue(CtxT<AT>* ctx, float lr) {
   if (ctx->ns > 1) {
     float lrs[TST_MAX_STACK];
     for (int i = 0; i < TST_MAX_STACK; ++i) lrs[i] = lr;
-    return opt_enqueue_stacked(ctx, lrs);
+    return opt_enqueue_stacked(ctx, lrs, tg);
   }
   ctx->opt_steps[0] += 1;
   // adam.py:406-414: bias corrections in host double precision, as python floats
@@ -2224,17 +2222,16 @@ int opt_enqueue(CtxT<AT>* ctx, float lr) {
   const double bc2 = 1.0 - pow((double)c.adam_beta2, (double)ctx->opt_steps[0]);
   if (ctx->full && ctx->gn_fused && ctx->gn_used + 3 * 1024 <= ctx->gn_cap) {
     // the layer matrices' sums of squares are in their slots; what is left: everything outside the per-layer regions
-    const int64_t first = ctx->layers[0].Wqkv - ctx->wb;
-    const int64_t per_layer = (int64_t)ctx->dqkv * ctx->d + (int64_t)ctx->d * ctx->dattn + (int64_t)ctx->Fgu * ctx->d + (int64_t)ctx->d * ctx->F;
-    const int64_t after = first + ctx->L * per_layer;
+    const int64_t first = ctx->layers[0].proj[P_QKV].W - ctx->wb;
+    const int64_t after = first + ctx->L * layer_numel(ctx);
     float* rest = ctx->gn_partial + ctx->gn_used;
     // (1024 / 2048 workgroups: 256 pulled the 2.1 GB of the embedding gradient at 2.3 TB/s)
-    CTX_RC(sumsq_partial(st, ctx->tg, first, rest, 1024));                                  // embedding side
-    CTX_RC(sumsq_partial(st, ctx->tg + after, ctx->n_train - after, rest + 1024, 2048));    // head (untied) + norm / bias tail
+    CTX_RC(sumsq_partial(st, tg, first, rest, 1024));                                  // embedding side
+    CTX_RC(sumsq_partial(st, tg + after, ctx->n_train - after, rest + 1024, 2048));    // head (untied) + norm / bias tail
     CTX_RC(clip_finalize(st, ctx->gn_partial, (int)(ctx->gn_used + 3 * 1024), c.max_grad_norm, ctx->clip_out));
     ctx->gn_fused = false;
   } else {
-    CTX_RC(grad_clip_coef(st, ctx->tg, ctx->n_train, c.max_grad_norm, ctx->clip_partial, clip_parts(ctx->n_train), ctx->clip_out));
+    CTX_RC(grad_clip_coef(st, tg, ctx->n_train, c.max_grad_norm, ctx->clip_partial, clip_parts(ctx->n_train), ctx->clip_out));
   }
   if (ctx->full) {
     // two parameter groups as HF builds them (trainer.py:1181-1196): weight decay on the matrices, none on the norm vectors;
@@ -2259,32 +2256,29 @@ int opt_enqueue(CtxT<AT>* ctx, float lr) {
     // (token embedding of an untied model, learned positions) goes through the flat kernel
     auto flat = [&](const AT* from, const AT* to, float wd) {
       const int64_t o = from - ctx->wb, n = to - from;
-      return n <= 0 ? TST_OK : adamw_step<AT>(os, ctx->tp + o, ctx->tg + o, ctx->tm + o, ctx->tv + o, n, ctx->clip_out, lr, c.adam_beta1, c.adam_beta2, c.adam_eps, wd,
+      return n <= 0 ? TST_OK : adamw_step<AT>(os, ctx->tp + o, tg + o, ctx->tm + o, ctx->tv + o, n, ctx->clip_out, lr, c.adam_beta1, c.adam_beta2, c.adam_eps, wd,
                                           b1, b2s, ctx->wb + o);
     };
     auto matrix = [&](AT* W, AT* WT, int rows, int cols) {
       if (!WT) return flat(W, W + (int64_t)rows * cols, c.weight_decay);   // (ctx->kmajor bit 0: no transposed copy to keep in step -- 30 B / param)
       const int64_t o = W - ctx->wb;
-      return adamw_step_matrix<AT>(os, ctx->tp + o, ctx->tg + o, ctx->tm + o, ctx->tv + o, rows, cols, ctx->clip_out, lr, c.adam_beta1, c.adam_beta2, c.adam_eps,
+      return adamw_step_matrix<AT>(os, ctx->tp + o, tg + o, ctx->tm + o, ctx->tv + o, rows, cols, ctx->clip_out, lr, c.adam_beta1, c.adam_beta2, c.adam_eps,
                                c.weight_decay, b1, b2s, W, WT);
     };
     const int d = ctx->d;
     const int slot_full = prof_begin(ctx, os, ctx->prof_hbm);
     // no-decay group first: norm vectors and biases of EVERY layer (a quarter of a million floats; layer 0's forward reads its share)
-    CTX_RC(adamw_step<AT>(os, ctx->tp + nd, ctx->tg + nd, ctx->tm + nd, ctx->tv + nd, nn, ctx->clip_out, lr, c.adam_beta1, c.adam_beta2, c.adam_eps, 0.0f, b1, b2s,
+    CTX_RC(adamw_step<AT>(os, ctx->tp + nd, tg + nd, ctx->tm + nd, ctx->tv + nd, nn, ctx->clip_out, lr, c.adam_beta1, c.adam_beta2, c.adam_eps, 0.0f, b1, b2s,
                       ctx->wb + nd));
     if (ctx->gpt2) {   // wte is also the head: [Vp, d] with its transpose; wpe flat
       CTX_RC(matrix(ctx->embed, ctx->lm_headT, ctx->Vp, d));
-      CTX_RC(flat(ctx->wpe, ctx->layers[0].Wqkv, c.weight_decay));
+      CTX_RC(flat(ctx->wpe, ctx->layers[0].proj[P_QKV].W, c.weight_decay));
     } else {
-      CTX_RC(flat(ctx->embed, ctx->layers[0].Wqkv, c.weight_decay));
+      CTX_RC(flat(ctx->embed, ctx->layers[0].proj[P_QKV].W, c.weight_decay));
     }
     CTX_RC(stage_done());
     for (auto& W : ctx->layers) {
-      CTX_RC(matrix(W.Wqkv, W.WqkvT, ctx->dqkv, d));
-      CTX_RC(matrix(W.Wo, W.WoT, d, ctx->dattn));
-      CTX_RC(matrix(W.Wgu, W.WguT, ctx->Fgu, d));
-      CTX_RC(matrix(W.Wd, W.WdT, d, ctx->F));
+      for (const ProjT<AT>& P : W.proj) CTX_RC(matrix(P.W, P.WT, P.dout, P.din));
       CTX_RC(stage_done());
     }
     if (!ctx->gpt2) CTX_RC(matrix(ctx->lm_head, ctx->lm_headT, ctx->Vp, d));
@@ -2295,7 +2289,7 @@ int opt_enqueue(CtxT<AT>* ctx, float lr) {
     return TST_OK;
   }
   const int slot = prof_begin(ctx, st, ctx->prof_hbm);
-  CTX_RC(adamw_step<AT>(st, ctx->tp, ctx->tg, ctx->tm, ctx->tv, ctx->n_train, ctx->clip_out, lr, c.adam_beta1, c.adam_beta2, c.adam_eps, c.weight_decay,
+  CTX_RC(adamw_step<AT>(st, ctx->tp, tg, ctx->tm, ctx->tv, ctx->n_train, ctx->clip_out, lr, c.adam_beta1, c.adam_beta2, c.adam_eps, c.weight_decay,
                     (float)bc1, (float)sqrt(bc2), nullptr));
   prof_end(ctx, st, slot, PROF_ADAMW, 1, 28.0 * ctx->n_train);
   CTX_RC(repack(ctx));
@@ -2328,10 +2322,7 @@ int train_step_dp_body(CtxT<AT>* ctx, const tst_batch* b, float lr, int32_t num_
     ctx->cur_items = num_items_global;
     CTX_RC(forward(ctx, true));
     CTX_RC(head_forward(ctx, true));
-    ctx->dp_in_step = true;
-    const int brc = backward(ctx, num_items_global);
-    ctx->dp_in_step = false;
-    if (brc != TST_OK) return brc;
+    CTX_RC(backward(ctx, num_items_global, nullptr, true));   // (the gradient regions are reduced as backward finishes them)
   } else {
     // this rank's shard carries no loss term: it contributes a zero gradient and still joins the collectives
     CTX_RC(opt_join(ctx));   // (no forward ran: the previous step's optimizer may still read the gradient)
@@ -2342,16 +2333,13 @@ int train_step_dp_body(CtxT<AT>* ctx, const tst_batch* b, float lr, int32_t num_
   if (!ctx->dp_regions.empty()) {
     if (!have_rows) {   // same collectives in the same order as the ranks that ran backward
       ctx->dp_next = 0;
-      ctx->dp_in_step = true;
-      const int jrc = regions_join(ctx);
-      ctx->dp_in_step = false;
-      if (jrc != TST_OK) return jrc;
+      CTX_RC(regions_join(ctx));
     }   // else: backward() reduced every region on the communication stream and joined it
   } else if (!ctx->zero_on) {
     CTX_RC(dp_allreduce(ctx, ctx->tg, (size_t)ctx->n_train, st));
   }   // (sharded optimizer state: the gradient is reduce-scattered inside the optimizer step)
   CTX_RC(dp_allreduce(ctx, ctx->d_loss, 1, st));
-  CTX_RC(opt_enqueue(ctx, lr));
+  CTX_RC(opt_enqueue(ctx, lr, ctx->tg));
   CTX_HIP(hipMemcpyAsync(&ctx->h_metrics[0], ctx->d_loss, 4, hipMemcpyDeviceToHost, st));
   CTX_HIP(hipMemcpyAsync(&ctx->h_metrics[TST_MAX_STACK], ctx->clip_out, 8, hipMemcpyDeviceToHost, st));
   return TST_OK;
@@ -2389,13 +2377,10 @@ int accumulate_async_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* num_
 template <typename AT>
 int optimizer_step_async_impl(CtxT<AT>* ctx, const float* lr) {
   const bool acc = ctx->acc_active;
-  if (acc) std::swap(ctx->tg, ctx->tacc);
-  int rc;
-  if (ctx->ns > 1) rc = opt_enqueue_stacked(ctx, lr);
-  else rc = opt_enqueue(ctx, lr[0]);
-  if (acc) std::swap(ctx->tg, ctx->tacc);
+  float* tg = acc ? ctx->tacc : ctx->tg;
   ctx->acc_active = false;
-  if (rc != TST_OK) return rc;
+  if (ctx->ns > 1) CTX_RC(opt_enqueue_stacked(ctx, lr, tg));
+  else CTX_RC(opt_enqueue(ctx, lr[0], tg));
   CTX_HIP(hipMemcpyAsync(&ctx->h_metrics[0], acc ? ctx->d_loss_acc : ctx->d_loss, 4 * TST_MAX_STACK, hipMemcpyDeviceToHost, ctx->stream));
   CTX_HIP(hipMemcpyAsync(&ctx->h_metrics[TST_MAX_STACK], ctx->clip_out, 8 * TST_MAX_STACK, hipMemcpyDeviceToHost, ctx->stream));
   return TST_OK;
@@ -2428,8 +2413,8 @@ int train_step_stacked_dp_body(CtxT<AT>* ctx, const tst_batch* b, const float* l
   if (!have_rows) CTX_HIP(hipMemsetAsync(ctx->tg, 0, (size_t)(ctx->n_train + TST_MAX_STACK) * sizeof(float), st));   // gradient and losses
   CTX_RC(dp_allreduce(ctx, ctx->tg, (size_t)ctx->n_train + TST_MAX_STACK, st));
   for (int sl = 0; sl < ctx->ns; ++sl) ctx->slot_steps[sl] = items_global[sl] > 0;   // the same decision on every rank
-  if (ctx->ns > 1) CTX_RC(opt_enqueue_stacked(ctx, lrs));
-  else if (ctx->slot_steps[0]) CTX_RC(opt_enqueue(ctx, lrs[0]));
+  if (ctx->ns > 1) CTX_RC(opt_enqueue_stacked(ctx, lrs, ctx->tg));
+  else if (ctx->slot_steps[0]) CTX_RC(opt_enqueue(ctx, lrs[0], ctx->tg));
   CTX_HIP(hipMemcpyAsync(&ctx->h_metrics[0], ctx->d_loss, 4 * TST_MAX_STACK, hipMemcpyDeviceToHost, st));
   CTX_HIP(hipMemcpyAsync(&ctx->h_metrics[TST_MAX_STACK], ctx->clip_out, 8 * TST_MAX_STACK, hipMemcpyDeviceToHost, st));
   return TST_OK;
@@ -2477,7 +2462,7 @@ int score_async_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* option_id
 // ---- greedy generation: prefill + max_new - 1 decode steps, all enqueued at once (include/tst_hip.h tst_generate_async)
 int gen_reserve(tst_ctx* ctx, int max_new) {
   if (ctx->gen_kv && max_new <= ctx->gen_cap_new) return TST_OK;
-  const tsthost::BatchLimits lim = {ctx->Tmax, ctx->Smax, ctx->Rmax, ctx->V, ctx->cfg.max_position, ctx->ns};
+  const tsthost::BatchLimits lim = batch_limits(ctx);
   if (ctx->gen_kv) {   // a larger max_new: nothing of the old buffers may be in flight
     CTX_RC(ctx_sync(ctx));
     ctx->pool.free_one(ctx->gen_kv, ctx->gen_kv_bytes);
@@ -2519,7 +2504,7 @@ int generate_async_impl(CtxT<AT>* ctx, const tst_batch* b, int32_t max_new, cons
   ctx->err.clear();
   // what a generation adds to a batch's checks is refused here, before an allocation or a launch (plan_generate walks cu_seqlens and seq_slot itself to build
   // the row map, so it repeats plan_batch's checks of those two)
-  const tsthost::BatchLimits lim = {ctx->Tmax, ctx->Smax, ctx->Rmax, ctx->V, ctx->cfg.max_position, ctx->ns};
+  const tsthost::BatchLimits lim = batch_limits(ctx);
   tsthost::GenPlan plan;
   {
     std::string perr;
@@ -2548,10 +2533,7 @@ int generate_async_impl(CtxT<AT>* ctx, const tst_batch* b, int32_t max_new, cons
     CTX_RC(logit_rows<AT>(st, ctx->logits, ctx->Vp, ctx->d_targets, S, ctx->V, ctx->stats, nullptr, 0, 0.f, nullptr, 0, ctx->optl));
     return next_token(st, ctx->stats, ctx->gen_dev, S, j, ctx->gen_tok, ctx->gen_logp, ctx->d_ids, ctx->d_pos, ctx->d_lab_idx);
   };
-  ctx->gen_mode = 1; ctx->gen_step = 0;
-  int rc = forward(ctx, false);
-  ctx->gen_mode = 0;
-  CTX_RC(rc);
+  CTX_RC(forward(ctx, false, GenPass{1, 0}));   // prefill
   CTX_RC(step_tail(0));
   if (max_new > 1) {
     // decode steps: the same forward() over one row per sequence. "Tokens" are sequences now: the slot boundaries are sequence counts, the head reads every row
@@ -2559,15 +2541,12 @@ int generate_async_impl(CtxT<AT>* ctx, const tst_batch* b, int32_t max_new, cons
     ctx->cur_maxlen = 1;
     for (int q = 0; q < TST_MAX_STACK; ++q) ctx->slot_ends.t_end[q] = ctx->row_ends.t_end[q] = plan.slot_s_end[q];
     double keys = (double)plan.T;
-    for (int j = 1; j < max_new && rc == TST_OK; ++j) {
+    for (int j = 1; j < max_new; ++j) {
       keys += S;
       ctx->cur_sumsq_len = keys;
-      ctx->gen_mode = 2; ctx->gen_step = j;
-      rc = forward(ctx, false);
-      ctx->gen_mode = 0;
-      if (rc == TST_OK) rc = step_tail(j);
+      CTX_RC(forward(ctx, false, GenPass{2, j}));
+      CTX_RC(step_tail(j));
     }
-    CTX_RC(rc);
   }
   float* h_out = (float*)(ctx->h_gen + ctx->gen_dev_bytes / 4);
   CTX_HIP(hipMemcpyAsync(h_out, ctx->gen_tok, (size_t)S * max_new * 4, hipMemcpyDeviceToHost, st));
@@ -2919,11 +2898,11 @@ static int fwd_bwd_enqueue(tst_ctx* ctx, const tst_batch* b, int32_t num_items) 
 
 // stacked folds: one clip + AdamW per slot that had labelled tokens in this batch (its own step count, learning rate and norm)
 static int opt_enqueue_stacked(tst_ctx* ctx, const float* lrs) {
-  return typed(ctx, [&](auto* c) { return opt_enqueue_stacked(c, lrs); });
+  return typed(ctx, [&](auto* c) { return opt_enqueue_stacked(c, lrs, c->tg); });
 }
 
 static int opt_enqueue(tst_ctx* ctx, float lr) {
-  return typed(ctx, [&](auto* c) { return opt_enqueue(c, lr); });
+  return typed(ctx, [&](auto* c) { return opt_enqueue(c, lr, c->tg); });
 }
 
 int tst_forward_backward(tst_ctx* ctx, const tst_batch* b, int32_t num_items, float* loss_out) {
