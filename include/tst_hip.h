@@ -361,6 +361,35 @@ int tst_generate_fetch(tst_ctx* ctx, int32_t* tokens_out /* [n_seqs, max_new_tok
 int tst_generate(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, const int32_t* eos_ids, int32_t n_eos, int32_t* tokens_out, float* logp_out,
                  int32_t* n_new_out);
 
+/* ---- token attribution: input-gradient saliency of s(x) ----
+ * Which tokens of a sequence carry its score. Position p predicts labels[p + 1]; rows(i) = the labelled rows of sequence i, n_i their number, z_r the fp32
+ * logits of row r. Per sequence (seq_kind[i]; NULL = all 0):
+ *   0, open form    J_i = (1 / n_i) sum_{r in rows(i)} log softmax(z_r)[target_r]              (log of the numeric / open s(x))
+ *   1, option form  J_i = z_r[target_r] - logsumexp_j z_r[option_ids[j]]                      (log of the multiple-choice s(x); exactly one labelled row,
+ *                                                                                               whose target is one of option_ids)
+ * With e[t, :] the embedding-layer output of token t (embed_tokens[id]; GPT-2: wte[id] + wpe[pos]) and g = d (sum_i J_i) / d e -- sequences of a packed batch do
+ * not interact, so one backward pass yields every sequence's own gradient -- the call returns, accumulated in fp32,
+ *   gxi_out[t]   = sum_d g[t, d] e[t, d]     (gradient x input, signed)
+ *   gnorm_out[t] = sqrt(sum_d g[t, d]^2)
+ * in the caller's token order (a token the model does not run, "trim_last_token", gets 0: nothing reads it under the causal mask) and logs_out[i] = J_i.
+ * Under bf16 gradient x input cancels and is the noisier of the two; gnorm is the robust output.
+ * Available on every context that can score (LoRA plain, forked, stacked with seq_slot as for tst_score_async; full fine-tune; bf16 and strict).
+ * tst_attribute_async enqueues a forward, the backward pass seeded with d (sum_i J_i) / d logits down to the embedding output, and the per-token reduction;
+ * tst_attribute_fetch waits for the attribution only (like tst_score_fetch). One attribution may be pending per context.
+ * The call reads weights and adapters only: trainables, optimizer state and step counts, the KV cache, a pending scoring pass and a pending generation are
+ * left as they are. The flat gradient (tst_get_grads, tst_grad_buffer) and the last-loss metrics (tst_fetch_loss, tst_fetch_metrics) are UNSPECIFIED afterwards:
+ * a tst_optimizer_step[_async] that would apply a gradient overwritten by an attribution returns TST_ESTATE (run tst_forward_backward again).
+ * Its small buffers (row weights, per-token results, pinned staging: 8 bytes per max_tokens + 8 per max_labelled + 1 KB on the device) are allocated by the
+ * first tst_attribute_async of a context -- like the KV cache of a generation -- and counted in tst_device_bytes.
+ * TST_ESTATE before anything is launched: weights not finalised, an open accumulation window, a context that has joined a data-parallel group;
+ * tst_attribute_fetch without a pending attribution. TST_EINVAL before anything is allocated or launched: the batch's own checks, no labelled token, n_opt
+ * outside 0 .. 256, an option id outside the vocabulary, a seq_kind other than 0 / 1, a kind-1 sequence whose labelled-row count is not 1 or whose target is not
+ * in option_ids, a kind-1 sequence with n_opt == 0. */
+int tst_attribute_async(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_kind /* [n_seqs] or NULL */, const int32_t* option_ids, int32_t n_opt);
+int tst_attribute_fetch(tst_ctx* ctx, float* gxi_out /* [n_tokens] */, float* gnorm_out /* [n_tokens] */, float* logs_out /* [n_seqs] */);
+int tst_attribute(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_kind, const int32_t* option_ids, int32_t n_opt, float* gxi_out, float* gnorm_out,
+                  float* logs_out);
+
 /* ---- measurement hooks (bench.py): HIP events on the ctx stream around the dominant kernel class ---- */
 /* on: bit 0 = bracket every dense contraction launch with HIP events on its stream; bit 1 = also bracket the HBM-bound kernel classes
  * (variant ids 101 AdamW, 102 SwiGLU, 103 RMSNorm / LayerNorm, 104 attention); 0 = off */

@@ -92,6 +92,17 @@ int tst_k_gelu_bwd(const void* dy, const void* x, void* dx, int64_t n);
 int tst_k_embed_pos(const int32_t* ids, const int32_t* pos, const void* E, const void* P, void* out, int T, int d, int vocab, int npos);
 int tst_k_logit_rows(const float* logits, int64_t ld, const int32_t* target, int n_rows, int V, float* stats, void* dlogits, int64_t ldd,
                      float inv_items, const int32_t* opt_ids, int n_opt, float* optl);
+/* token attribution kernels (csrc/attribute.hip); every pointer is a device pointer, the _f32 forms are the strict-mode instances.
+ * attr_seed: dlogits[r, 0 .. Vp) (bf16 / fp32, padding columns exactly 0) = row_w[r] (onehot(target[r]) - softmax(logits[r, 0 .. V))) for row_kind[r] == 0; for
+ * row_kind[r] == 1 the softmax runs over the n_opt <= 256 columns opt_ids only and every other column is 0. stats[r] = {lse, logit[target], option logsumexp, max}.
+ * Needs Vp >= V, Vp % 4 == 0, ld and ldd >= Vp and multiples of 4; targets and option ids inside [0, V) are the caller's to guarantee.
+ * token_attr: gxi[t] = sum_c g[t, c] e[t, c], gnorm[t] = sqrt(sum_c g[t, c]^2), rows of d elements (d % 8 == 0, d <= 8192), fp32 accumulation, bit-reproducible. */
+int tst_k_attr_seed(const float* logits, int64_t ld, const int32_t* target, const float* row_w, const int32_t* row_kind, const int32_t* opt_ids, int n_opt, int n_rows,
+                    int V, int Vp, float* stats, void* dlogits, int64_t ldd);
+int tst_k_attr_seed_f32(const float* logits, int64_t ld, const int32_t* target, const float* row_w, const int32_t* row_kind, const int32_t* opt_ids, int n_opt,
+                        int n_rows, int V, int Vp, float* stats, float* dlogits, int64_t ldd);
+int tst_k_token_attr(const void* g, const void* e, int T, int d, float* gxi, float* gnorm);
+int tst_k_token_attr_f32(const float* g, const float* e, int T, int d, float* gxi, float* gnorm);
 int tst_k_attn_fwd(const void* qkv, int64_t ld, const int32_t* cu, int n_seqs, int max_len, void* out, int64_t ldo, float* lse, int T, int H,
                    int Hkv, int dh, float scale);
 int tst_k_attn_bwd(const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dO, int64_t lddo, const float* lse, float* delta,

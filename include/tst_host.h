@@ -47,6 +47,15 @@ int tst_host_plan_generate(const tst_model_cfg* cfg, const tst_batch* b, int max
  * n_new_out[s] counts the eos token), in place */
 int tst_host_cut_at_eos(int32_t* tokens, float* logp, int32_t* n_new_out, int n_seqs, int max_new, const int32_t* eos_ids, int n_eos);
 
+/* tsthost::plan_attribute (token attribution, include/tst_hip.h tst_attribute_async): the checks an attribution adds to a batch's own, and for every labelled
+ * row -- by sequence, then by position -- its weight 1 / n_i, its kind and its sequence. The three outputs hold one entry per labelled token of the batch and
+ * may each be NULL; err_out / err_cap receive the message of a refusal. Returns TST_OK or TST_EINVAL. */
+int tst_host_plan_attribute(const tst_model_cfg* cfg, const tst_batch* b, const int32_t* seq_kind, const int32_t* option_ids, int n_opt, int32_t* n_rows_out,
+                            float* row_w_out, int32_t* row_kind_out, int32_t* row_seq_out, char* err_out, int err_cap);
+/* the fetch side of an attribution: per-token values of the tokens the device ran (sequence s at [cu_dev[s], cu_dev[s + 1])) into the caller's token order
+ * (sequence s at [cu_src[s], cu_src[s + 1])); a token the device did not run (trim_last_token) gets 0. TST_EINVAL when a sequence is longer on the device. */
+int tst_host_untrim_tokens(const float* src, const int32_t* cu_dev, const int32_t* cu_src, int n_seqs, float* dst);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

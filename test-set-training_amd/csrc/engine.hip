@@ -295,6 +295,17 @@ struct tst_ctx {
   hipEvent_t gen_evt = nullptr; // recorded behind the result copies: tst_generate_fetch waits for it, not for the stream
   int gen_S = -1, gen_new = 0;  // pending generation (-1: none)
   std::vector<int> gen_eos;
+  // Token attribution (tst_attribute_async; kernels in attribute.hip, row weights and the fetch side in host_logic.h). Allocated by the first attribution of the
+  // context. attr_dev = row weights [Rmax] | row kinds [Rmax] | option ids [256] | gxi [Tmax] | gnorm [Tmax] (4-byte words); h_attr = the pinned staging image of the
+  // first three, then gxi | gnorm | row statistics [Rmax * 4] of the pending attribution. attr_pass: backward() runs for an attribution (seeded by attr_seed, the
+  // gradient of layer 0's input formed in LoRA contexts too, no embedding gradient). grad_stale: the flat gradient no longer holds a training step's gradient.
+  float* attr_dev = nullptr;
+  float* h_attr = nullptr;
+  hipEvent_t attr_evt = nullptr;   // recorded behind the result copies: tst_attribute_fetch waits for it, not for the stream
+  int attr_S = -1, attr_nopt = 0;  // pending attribution (-1: none)
+  bool attr_pass = false, grad_stale = false;
+  tsthost::AttrPlan attr_plan;
+  std::vector<int> attr_cu_dev, attr_cu_src;
   float* d_loss = nullptr;
   int cur_T = 0, cur_S = 0, cur_R = 0, cur_maxlen = 0, cur_items = 0;
   double cur_sumsq_len = 0;   // sum over the batch's sequences of length^2 (attention work)
@@ -1238,6 +1249,9 @@ int backward(CtxT<AT>* ctx, int num_items, const int32_t* slot_items = nullptr, 
   const float scale = 1.0f / sqrtf((float)ctx->dh);
   const float inv_items = 1.0f / (float)num_items;
   const bool full = ctx->full;
+  // An attribution (attribute_async_impl) is this pass with two differences: the seed is d (sum_i log s(x_i)) / d logits instead of the loss gradient, and the
+  // gradient of layer 0's input is formed in LoRA contexts too. The weight- and adapter-gradient contractions stay in: the flat gradient is unspecified afterwards.
+  const bool attr = ctx->attr_pass;
   CTX_RC(opt_join(ctx));     // (a no-op behind head_forward: backward overwrites the gradient a pending optimizer step reads)
   ctx->dw_side_open = false;
   ctx->ndw_open[0] = ctx->ndw_open[1] = false;
@@ -1254,11 +1268,17 @@ int backward(CtxT<AT>* ctx, int num_items, const int32_t* slot_items = nullptr, 
     if (ctx->gn_fused) CTX_HIP(hipMemsetAsync(ctx->gn_partial, 0, (size_t)ctx->gn_cap * sizeof(float), st));
     // regions that are accumulated with atomics start from zero: embedding rows and the norm vectors
     // (GPT-2: the token-embedding gradient starts as the tied head's dW, written below, so only wpe is cleared)
-    if (ctx->gpt2) CTX_HIP(hipMemsetAsync(gof(ctx->wpe), 0, (size_t)ctx->npos * d * sizeof(float), st));
+    // (an attribution reads dX itself and forms no embedding gradient: nothing to clear)
+    if (attr) {
+    } else if (ctx->gpt2) CTX_HIP(hipMemsetAsync(gof(ctx->wpe), 0, (size_t)ctx->npos * d * sizeof(float), st));
     else CTX_HIP(hipMemsetAsync(gof(ctx->embed), 0, (size_t)ctx->Vp * d * sizeof(float), st));
     CTX_HIP(hipMemsetAsync(ctx->tg + ctx->n_decay, 0, (size_t)(ctx->n_train - ctx->n_decay) * sizeof(float), st));
   }
-  if (ctx->ns == 1) {
+  if (attr) {
+    const int* kinds = (const int*)ctx->attr_dev + ctx->Rmax;
+    CTX_RC(attr_seed<AT>(st, ctx->logits, ctx->Vp, ctx->d_targets, ctx->attr_dev, kinds, kinds + ctx->Rmax, ctx->attr_nopt, R, ctx->V, ctx->Vp, ctx->stats, ctx->dlogits,
+                         ctx->Vp));
+  } else if (ctx->ns == 1) {
     CTX_RC(logit_rows<AT>(st, ctx->logits, ctx->Vp, ctx->d_targets, R, ctx->V, ctx->stats, ctx->dlogits, ctx->Vp, inv_items, nullptr, 0, nullptr));
     CTX_RC(loss_reduce(st, ctx->stats, R, inv_items, ctx->d_loss));
   } else {
@@ -1339,7 +1359,8 @@ int backward(CtxT<AT>* ctx, int num_items, const int32_t* slot_items = nullptr, 
     if (!ctx->gpt2 && !rope_in) CTX_RC(rope_apply<AT>(st, ctx->dqkv_b, ctx->d_pos, ctx->cosT, ctx->sinT, T, ctx->H + ctx->Hkv, ctx->dh, ctx->dqkv, 1));
     if (full && W.bqkv) CTX_RC(colsum<AT>(st, ctx->dqkv_b, ctx->dqkv, gof(W.bqkv), T, ctx->dqkv, ctx->colred_ws));
     // LoRA: the embedding is frozen, so the gradient of layer 0's INPUT has no reader: its q|k|v projection's dX contraction and the norm backward behind it are skipped
-    const bool input_grad = full || l > 0;
+    // (an attribution is after exactly that gradient)
+    const bool input_grad = full || l > 0 || attr;
     AT* dxq = ctx->dxn;
     CTX_RC(ndw_wait(ctx, 0));   // (this layer's MLP-norm reduction on the side stream reads dxn)
     CTX_RC(linear_bwd<AT>(ctx, ctx->dqkv_b, W.xn1, W.proj[P_QKV], W.us_qkv, dxq, rows, gof(W.proj[P_QKV].W), 3, input_grad));
@@ -1372,8 +1393,8 @@ int backward(CtxT<AT>* ctx, int num_items, const int32_t* slot_items = nullptr, 
     CTX_HIP(hipStreamWaitEvent(st, ctx->ev_join, 0));
     ctx->ndw_open[0] = ctx->ndw_open[1] = false;
   }
-  if (full) CTX_RC(embed_bwd<AT>(st, ctx->d_ids, ctx->dX, gof(ctx->embed), T, d, ctx->V));
-  if (full && ctx->gpt2) CTX_RC(embed_bwd<AT>(st, ctx->d_pos, ctx->dX, gof(ctx->wpe), T, d, ctx->npos));
+  if (full && !attr) CTX_RC(embed_bwd<AT>(st, ctx->d_ids, ctx->dX, gof(ctx->embed), T, d, ctx->V));
+  if (full && !attr && ctx->gpt2) CTX_RC(embed_bwd<AT>(st, ctx->d_pos, ctx->dX, gof(ctx->wpe), T, d, ctx->npos));
   if (regions) CTX_RC(regions_join(ctx));   // embedding side and the norm / bias tail, then the main stream waits for the reduction
   CTX_RC(lora_unpack_grad<AT>(st, ctx->descs_dev, (int)ctx->descs.size(), ctx->tg, ctx->pack_max_elems));
   return TST_OK;
@@ -2117,6 +2138,7 @@ int fwd_bwd_enqueue(CtxT<AT>* ctx, const tst_batch* b, int32_t num_items, const 
   }
   const int items = num_items > 0 ? num_items : ctx->cur_R;
   ctx->cur_items = items;
+  ctx->grad_stale = false;
   CTX_RC(forward(ctx, true));
   CTX_RC(head_forward(ctx, true));
   return backward(ctx, items, slot_items);
@@ -2377,6 +2399,7 @@ int accumulate_async_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* num_
 template <typename AT>
 int optimizer_step_async_impl(CtxT<AT>* ctx, const float* lr) {
   const bool acc = ctx->acc_active;
+  if (!acc && ctx->grad_stale) return fail(ctx, TST_ESTATE, "an attribution has overwritten the gradient of the last tst_forward_backward: run it again before the optimizer step");
   float* tg = acc ? ctx->tacc : ctx->tg;
   ctx->acc_active = false;
   if (ctx->ns > 1) CTX_RC(opt_enqueue_stacked(ctx, lr, tg));
@@ -2558,6 +2581,72 @@ int generate_async_impl(CtxT<AT>* ctx, const tst_batch* b, int32_t max_new, cons
   return TST_OK;
 }
 
+// ---- token attribution (include/tst_hip.h tst_attribute_async): forward with the stash, head, the backward pass seeded with d (sum_i log s(x_i)) / d logits
+// down to the gradient of layer 0's input, then one reduction per token
+int attr_reserve(tst_ctx* ctx) {
+  if (ctx->attr_dev) return TST_OK;
+  const int64_t words = 2 * (int64_t)ctx->Rmax + tsthost::kAttrMaxOpt + 2 * (int64_t)ctx->Tmax;
+  float* dev = (float*)ctx->pool.alloc(words * 4);
+  if (!dev) return fail(ctx, TST_ENOMEM, "hipMalloc failed: attribution buffers");
+  CTX_HIP(hipStreamSynchronize(nullptr));   // the pool zero-fills on the null stream: it must not land behind this attribution's first writes
+  if (!ctx->h_attr) CTX_HIP(hipHostMalloc((void**)&ctx->h_attr, (size_t)(words + 4 * (int64_t)ctx->Rmax) * 4, hipHostMallocDefault));
+  if (!ctx->attr_evt) CTX_HIP(hipEventCreateWithFlags(&ctx->attr_evt, hipEventDisableTiming));
+  CTX_HIP(hipEventRecord(ctx->attr_evt, ctx->stream));
+  ctx->attr_dev = dev;
+  return TST_OK;
+}
+
+template <typename AT>
+int attribute_async_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* seq_kind, const int32_t* option_ids, int32_t n_opt) {
+  if (!b) return TST_EINVAL;
+  if (!ctx->finalized) return fail(ctx, TST_ESTATE, "weights not finalised");
+  if (ctx->acc_active) return fail(ctx, TST_ESTATE, "an accumulation window is open on this context: an attribution would overwrite the micro-batch gradient path");
+  if (ctx->dp_comm) return fail(ctx, TST_ESTATE, "attribution on a context that has joined a data-parallel group is not supported");
+  ctx->err.clear();
+  tsthost::AttrPlan plan;
+  {
+    std::string perr;
+    if (tsthost::plan_attribute(b, batch_limits(ctx), seq_kind, option_ids, n_opt, plan, perr) != TST_OK) return fail(ctx, TST_EINVAL, perr);
+  }
+  CTX_RC(upload_batch(ctx, b, true, nullptr, 0));   // (the batch's own checks: nothing is copied or allocated for a refused batch)
+  if (ctx->cur_R != plan.R) return fail(ctx, TST_EINVAL, "internal: labelled rows of plan_batch and plan_attribute differ");
+  ctx->attr_S = -1;
+  CTX_RC(attr_reserve(ctx));
+  CTX_RC(ctx_event_sync(ctx, ctx->attr_evt));   // the staging image may still feed the previous attribution's copies
+  hipStream_t st = ctx->stream;
+  const int R = plan.R, S = ctx->cur_S, T = ctx->cur_T, Rmax = ctx->Rmax, Tmax = ctx->Tmax;
+  const size_t head_words = 2 * (size_t)Rmax + tsthost::kAttrMaxOpt;
+  {
+    float* h = ctx->h_attr;
+    memcpy(h, plan.row_w.data(), sizeof(float) * (size_t)R);
+    memcpy(h + Rmax, plan.row_kind.data(), sizeof(int) * (size_t)R);
+    if (n_opt > 0) memcpy(h + 2 * (size_t)Rmax, option_ids, sizeof(int) * (size_t)n_opt);
+    CTX_HIP(hipMemcpyAsync(ctx->attr_dev, h, head_words * 4, hipMemcpyHostToDevice, st));
+  }
+  ctx->attr_nopt = n_opt;
+  const int* h_cu = ctx->cur_stage + 2 * Tmax;
+  ctx->attr_cu_dev.assign(h_cu, h_cu + S + 1);
+  ctx->attr_cu_src.assign(b->cu_seqlens, b->cu_seqlens + S + 1);
+  ctx->grad_stale = true;
+  CTX_RC(forward(ctx, true));
+  CTX_RC(head_forward(ctx, true));
+  ctx->attr_pass = true;
+  const int brc = backward(ctx, R);
+  ctx->attr_pass = false;
+  CTX_RC(brc);
+  // (backward has joined its side streams: dX is the gradient of layer 0's stashed input, the embedding-layer output -- for GPT-2 wte + wpe)
+  float* gxi = ctx->attr_dev + head_words;
+  CTX_RC(token_attr<AT>(st, ctx->dX, ctx->layers[0].x_in, T, ctx->d, gxi, gxi + Tmax));
+  float* h_res = ctx->h_attr + head_words;
+  CTX_HIP(hipMemcpyAsync(h_res, gxi, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+  CTX_HIP(hipMemcpyAsync(h_res + Tmax, gxi + Tmax, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+  CTX_HIP(hipMemcpyAsync(h_res + 2 * (size_t)Tmax, ctx->stats, (size_t)R * 16, hipMemcpyDeviceToHost, st));
+  CTX_HIP(hipEventRecord(ctx->attr_evt, st));
+  ctx->attr_plan = std::move(plan);
+  ctx->attr_S = S;
+  return TST_OK;
+}
+
 template <typename AT>
 int forward_logits_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* rows, int32_t n_rows, float* logits_out) {
   if (!b || !rows || !logits_out || n_rows <= 0) return TST_EINVAL;
@@ -2729,6 +2818,8 @@ int tst_destroy(tst_ctx* ctx) {
   if (ctx->h_metrics) (void)hipHostFree(ctx->h_metrics);
   if (ctx->h_score) (void)hipHostFree(ctx->h_score);
   if (ctx->h_gen) (void)hipHostFree(ctx->h_gen);
+  if (ctx->h_attr) (void)hipHostFree(ctx->h_attr);
+  if (ctx->attr_evt) (void)hipEventDestroy(ctx->attr_evt);
   if (ctx->gen_evt) (void)hipEventDestroy(ctx->gen_evt);
   if (ctx->score_evt) (void)hipEventDestroy(ctx->score_evt);
   if (ctx->h_opt_ids) (void)hipHostFree(ctx->h_opt_ids);
@@ -3090,6 +3181,33 @@ int tst_score(tst_ctx* ctx, const tst_batch* b, const int32_t* option_ids, int32
   int rc = tst_score_async(ctx, b, option_ids, n_opt);
   if (rc != TST_OK) return rc;
   return tst_score_fetch(ctx, logp_out, correct_out, opt_logit_out, row_seq_out, n_rows_out);
+}
+
+int tst_attribute_async(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_kind, const int32_t* option_ids, int32_t n_opt) {
+  if (!ctx || !b) return TST_EINVAL;
+  return typed(ctx, [&](auto* c) { return attribute_async_impl(c, b, seq_kind, option_ids, n_opt); });
+}
+
+int tst_attribute_fetch(tst_ctx* ctx, float* gxi_out, float* gnorm_out, float* logs_out) {
+  if (!ctx) return TST_EINVAL;
+  if (ctx->attr_S < 0) return fail(ctx, TST_ESTATE, "tst_attribute_fetch without a pending tst_attribute_async");
+  CTX_RC(ctx_event_sync(ctx, ctx->attr_evt));   // work enqueued after the attribution keeps running
+  const int S = ctx->attr_S;
+  ctx->attr_S = -1;
+  const float* h_res = ctx->h_attr + 2 * (size_t)ctx->Rmax + tsthost::kAttrMaxOpt;
+  // the caller's token order: a token trim_last_token kept off the device gets 0 (nothing reads it under the causal mask: its gradient is exactly 0)
+  if (gxi_out && tsthost::untrim_tokens(h_res, ctx->attr_cu_dev.data(), ctx->attr_cu_src.data(), S, gxi_out) != TST_OK) return fail(ctx, TST_EINVAL, "internal: un-trim map");
+  if (gnorm_out && tsthost::untrim_tokens(h_res + ctx->Tmax, ctx->attr_cu_dev.data(), ctx->attr_cu_src.data(), S, gnorm_out) != TST_OK)
+    return fail(ctx, TST_EINVAL, "internal: un-trim map");
+  if (logs_out) tsthost::attr_logs(h_res + 2 * (size_t)ctx->Tmax, ctx->attr_plan, S, logs_out);
+  return TST_OK;
+}
+
+int tst_attribute(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_kind, const int32_t* option_ids, int32_t n_opt, float* gxi_out, float* gnorm_out,
+                  float* logs_out) {
+  int rc = tst_attribute_async(ctx, b, seq_kind, option_ids, n_opt);
+  if (rc != TST_OK) return rc;
+  return tst_attribute_fetch(ctx, gxi_out, gnorm_out, logs_out);
 }
 
 int tst_generate_async(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, const int32_t* eos_ids, int32_t n_eos) {

@@ -88,4 +88,28 @@ int tst_host_cut_at_eos(int32_t* tokens, float* logp, int32_t* n_new_out, int n_
   return TST_OK;
 }
 
+int tst_host_plan_attribute(const tst_model_cfg* cfg, const tst_batch* b, const int32_t* seq_kind, const int32_t* option_ids, int n_opt, int32_t* n_rows_out,
+                            float* row_w_out, int32_t* row_kind_out, int32_t* row_seq_out, char* err_out, int err_cap) {
+  if (!cfg) return TST_EINVAL;
+  tsthost::AttrPlan p;
+  std::string err;
+  const int rc = tsthost::plan_attribute(b, limits_of(*cfg), seq_kind, option_ids, n_opt, p, err);
+  if (err_out && err_cap > 0) {
+    strncpy(err_out, err.c_str(), (size_t)err_cap - 1);
+    err_out[err_cap - 1] = 0;
+  }
+  if (rc != TST_OK) return rc;
+  if (n_rows_out) *n_rows_out = p.R;
+  for (int r = 0; r < p.R; ++r) {
+    if (row_w_out) row_w_out[r] = p.row_w[(size_t)r];
+    if (row_kind_out) row_kind_out[r] = p.row_kind[(size_t)r];
+    if (row_seq_out) row_seq_out[r] = p.row_seq[(size_t)r];
+  }
+  return TST_OK;
+}
+
+int tst_host_untrim_tokens(const float* src, const int32_t* cu_dev, const int32_t* cu_src, int n_seqs, float* dst) {
+  return tsthost::untrim_tokens(src, cu_dev, cu_src, n_seqs, dst);
+}
+
 }  // extern "C"

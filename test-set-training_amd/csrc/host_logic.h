@@ -301,4 +301,78 @@ inline void cut_at_eos(int32_t* tokens, float* logp, int32_t* n_new, int S, int 
   }
 }
 
+// ------------------------------------------------------------------------------------------------ token attribution: validation, row weights, the fetch side
+// An attribution (include/tst_hip.h tst_attribute_async) differentiates J = sum_i J_i, J_i = log s(x_i): the mean log-probability of sequence i's labelled rows
+// (kind 0, the open form) or logit[target] - logsumexp over option_ids on its ONE labelled row (kind 1, the option form). plan_attribute refuses what the engine
+// cannot run BEFORE anything is launched and gives every labelled row -- in plan_batch's order: by sequence, then by position -- its weight 1 / n_i and its kind.
+// Ids, labels and lengths against the vocabulary / max_position and the context's capacities stay plan_batch's to check; input_ids is never dereferenced.
+constexpr int kAttrMaxOpt = 256;
+struct AttrPlan {
+  int R = 0;
+  std::vector<float> row_w;
+  std::vector<int> row_kind, row_seq;
+};
+inline int plan_attribute(const tst_batch* b, const BatchLimits& lim, const int32_t* seq_kind, const int32_t* option_ids, int n_opt, AttrPlan& out, std::string& err) {
+  auto fail = [&](const char* m) { err = m; return TST_EINVAL; };
+  if (!b) return fail("null batch");
+  if (n_opt < 0 || n_opt > kAttrMaxOpt || (n_opt > 0 && !option_ids)) return fail("n_opt out of range (0..256), or a null option list");
+  for (int j = 0; j < n_opt; ++j)
+    if (option_ids[j] < 0 || option_ids[j] >= lim.V) return fail("option id out of vocabulary");
+  const int T = b->n_tokens, S = b->n_seqs;
+  if (T <= 0 || S <= 0 || T > lim.Tmax || S > lim.Smax) return fail("batch exceeds max_tokens/max_seqs or is empty");
+  if (!b->input_ids || !b->cu_seqlens) return fail("null batch pointers");
+  if (!b->labels) return fail("labels required");
+  if (b->cu_seqlens[0] != 0 || b->cu_seqlens[S] != T) return fail("cu_seqlens must start at 0 and end at n_tokens");
+  out.R = 0;
+  out.row_w.clear(); out.row_kind.clear(); out.row_seq.clear();
+  for (int s = 0; s < S; ++s) {
+    const int s0 = b->cu_seqlens[s], s1 = b->cu_seqlens[s + 1];
+    if (s0 < 0 || s1 > T || s1 < s0) return fail("cu_seqlens must be non-decreasing and within n_tokens");
+    const int kind = seq_kind ? seq_kind[s] : 0;
+    if (kind != 0 && kind != 1) return fail("seq_kind must be 0 (open form) or 1 (option form)");
+    if (kind == 1 && n_opt == 0) return fail("an option-form sequence needs option ids (n_opt == 0)");
+    int n = 0, tgt = -1;
+    for (int p = s0 + 1; p < s1; ++p)
+      if (b->labels[p] != -100) { ++n; tgt = b->labels[p]; }
+    if (kind == 1) {
+      if (n != 1) return fail("an option-form sequence must have exactly one labelled token");
+      bool found = false;
+      for (int j = 0; j < n_opt && !found; ++j) found = option_ids[j] == tgt;
+      if (!found) return fail("the target of an option-form sequence is not one of the option ids");
+    }
+    for (int q = 0; q < n; ++q) {
+      out.row_w.push_back(kind == 1 ? 1.0f : 1.0f / (float)n);
+      out.row_kind.push_back(kind);
+      out.row_seq.push_back(s);
+    }
+    out.R += n;
+  }
+  if (out.R == 0) return fail("batch has no labelled tokens");
+  return TST_OK;
+}
+// J_i of every sequence from the rows the seed kernel leaves, stats[r] = {lse, logit[target], option logsumexp, max}: sequences without a labelled row get 0
+inline void attr_logs(const float* stats, const AttrPlan& p, int S, float* logs_out) {
+  std::vector<double> acc((size_t)S, 0.0);
+  for (int r = 0; r < p.R; ++r) {
+    const float* st = stats + (size_t)r * 4;
+    const double j = p.row_kind[(size_t)r] ? (double)st[1] - (double)st[2] : (double)st[1] - (double)st[0];
+    acc[(size_t)p.row_seq[(size_t)r]] += (double)p.row_w[(size_t)r] * j;
+  }
+  for (int s = 0; s < S; ++s) logs_out[s] = (float)acc[(size_t)s];
+}
+// Per-token results back into the caller's token order: the device ran the tokens [cu_dev[s], cu_dev[s + 1]) of sequence s, the caller's batch holds it at
+// [cu_src[s], cu_src[s + 1]) (trim_last_token: one token more, the last one); a token the device did not run gets 0. TST_EINVAL when the two maps do not fit.
+inline int untrim_tokens(const float* src, const int32_t* cu_dev, const int32_t* cu_src, int S, float* dst) {
+  if (!src || !cu_dev || !cu_src || !dst || S < 0) return TST_EINVAL;
+  for (int s = 0; s < S; ++s) {
+    const int nd = cu_dev[s + 1] - cu_dev[s], ns = cu_src[s + 1] - cu_src[s];
+    if (cu_dev[s] < 0 || cu_src[s] < 0 || nd < 0 || ns < nd) return TST_EINVAL;
+  }
+  for (int s = 0; s < S; ++s) {
+    const int nd = cu_dev[s + 1] - cu_dev[s], ns = cu_src[s + 1] - cu_src[s];
+    for (int p = 0; p < ns; ++p) dst[cu_src[s] + p] = p < nd ? src[cu_dev[s] + p] : 0.0f;
+  }
+  return TST_OK;
+}
+
 }  // namespace tsthost

@@ -273,8 +273,75 @@ static void test_plan_generate() {
   CHECK(n_new[1] == 4);
 }
 
+// token attribution: the row weights / kinds of plan_attribute, its refusals, and the un-trim of the fetch side
+static void test_attribute() {
+  // three sequences of 1, 2 and 5 tokens; labels on the last token of the second and on the last three of the third
+  const int32_t cu[4] = {0, 1, 3, 8};
+  const int32_t ids[8] = {1, 2, 3, 4, 5, 6, 7, 8};
+  const int32_t lab[8] = {9, -100, 7, -100, -100, 3, 4, 5};   // (a label on a sequence's first token predicts nothing: not a row)
+  tst_batch b;
+  memset(&b, 0, sizeof(b));
+  b.input_ids = ids; b.labels = lab; b.cu_seqlens = cu; b.n_seqs = 3; b.n_tokens = 8;
+  const BatchLimits lim = {16, 4, 8, 50, 16, 1};
+  const int32_t opt[3] = {2, 7, 11};
+  const int32_t kind[3] = {0, 1, 0};
+  AttrPlan p;
+  std::string err;
+  CHECK(plan_attribute(&b, lim, kind, opt, 3, p, err) == TST_OK);
+  CHECK(p.R == 4 && p.row_w.size() == 4 && p.row_kind.size() == 4 && p.row_seq.size() == 4);
+  if (p.R == 4) {
+    CHECK(p.row_seq[0] == 1 && p.row_kind[0] == 1 && p.row_w[0] == 1.0f);
+    for (int r = 1; r < 4; ++r) CHECK(p.row_seq[(size_t)r] == 2 && p.row_kind[(size_t)r] == 0 && p.row_w[(size_t)r] == 1.0f / 3.0f);
+    const float stats[16] = {5.f, 2.f, 3.f, 0.f, 4.f, 1.f, 0.f, 0.f, 4.f, 2.f, 0.f, 0.f, 4.f, 3.f, 0.f, 0.f};
+    float logs[3] = {-1.f, -1.f, -1.f};
+    attr_logs(stats, p, 3, logs);
+    CHECK(logs[0] == 0.0f && logs[1] == -1.0f && fabsf(logs[2] - (-2.0f)) < 1e-6f);
+  }
+  CHECK(plan_attribute(&b, lim, nullptr, nullptr, 0, p, err) == TST_OK && p.R == 4 && p.row_kind[0] == 0);
+  // refusals
+  CHECK(plan_attribute(&b, lim, kind, opt, 0, p, err) == TST_EINVAL && err.find("n_opt == 0") != std::string::npos);
+  CHECK(plan_attribute(&b, lim, kind, opt, kAttrMaxOpt + 1, p, err) == TST_EINVAL && err.find("n_opt") != std::string::npos);
+  CHECK(plan_attribute(&b, lim, kind, opt, -1, p, err) == TST_EINVAL);
+  const int32_t bad_opt[2] = {2, 50};
+  CHECK(plan_attribute(&b, lim, kind, bad_opt, 2, p, err) == TST_EINVAL && err.find("option id") != std::string::npos);
+  const int32_t miss[2] = {2, 11};
+  CHECK(plan_attribute(&b, lim, kind, miss, 2, p, err) == TST_EINVAL && err.find("not one of the option ids") != std::string::npos);
+  const int32_t kind3[3] = {0, 0, 1};
+  CHECK(plan_attribute(&b, lim, kind3, opt, 3, p, err) == TST_EINVAL && err.find("exactly one") != std::string::npos);
+  const int32_t kind0[3] = {1, 0, 0};
+  CHECK(plan_attribute(&b, lim, kind0, opt, 3, p, err) == TST_EINVAL && err.find("exactly one") != std::string::npos);
+  const int32_t kindx[3] = {0, 2, 0};
+  CHECK(plan_attribute(&b, lim, kindx, opt, 3, p, err) == TST_EINVAL && err.find("seq_kind") != std::string::npos);
+  const int32_t nolab[8] = {9, -100, -100, -100, -100, -100, -100, -100};
+  tst_batch e = b;
+  e.labels = nolab;
+  CHECK(plan_attribute(&e, lim, nullptr, nullptr, 0, p, err) == TST_EINVAL && err.find("no labelled") != std::string::npos);
+  e.labels = nullptr;
+  CHECK(plan_attribute(&e, lim, nullptr, nullptr, 0, p, err) == TST_EINVAL && err.find("labels required") != std::string::npos);
+  CHECK(plan_attribute(nullptr, lim, nullptr, nullptr, 0, p, err) == TST_EINVAL);
+  // un-trim: lengths 1 (never trimmed), 2 and 5, trimmed and untrimmed
+  const float src[6] = {1.f, 2.f, 3.f, 4.f, 5.f, 6.f};
+  const int32_t cu_trim[4] = {0, 1, 2, 6};
+  float dst[8];
+  for (float& v : dst) v = -7.f;
+  CHECK(untrim_tokens(src, cu_trim, cu, 3, dst) == TST_OK);
+  const float want[8] = {1.f, 2.f, 0.f, 3.f, 4.f, 5.f, 6.f, 0.f};
+  for (int t = 0; t < 8; ++t) CHECK(dst[t] == want[t]);
+  const float src8[8] = {1.f, 2.f, 3.f, 4.f, 5.f, 6.f, 7.f, 8.f};
+  CHECK(untrim_tokens(src8, cu, cu, 3, dst) == TST_OK);
+  for (int t = 0; t < 8; ++t) CHECK(dst[t] == src8[t]);
+  const int32_t cu1[2] = {0, 1}, cu2[2] = {0, 2};
+  float one[2] = {-7.f, -7.f};
+  CHECK(untrim_tokens(src, cu1, cu1, 1, one) == TST_OK && one[0] == 1.f && one[1] == -7.f);
+  CHECK(untrim_tokens(src, cu1, cu2, 1, one) == TST_OK && one[0] == 1.f && one[1] == 0.f);
+  CHECK(untrim_tokens(src, cu2, cu1, 1, one) == TST_EINVAL);   // longer on the device than in the caller's batch
+  CHECK(untrim_tokens(src, cu1, cu1, 0, one) == TST_OK);
+  CHECK(untrim_tokens(nullptr, cu1, cu1, 1, one) == TST_EINVAL);
+}
+
 int main() {
   test_plan_generate();
+  test_attribute();
   test_plan_batch();
   test_zero_and_layout();
   if (g_fail) { fprintf(stderr, "%d checks failed\n", g_fail); return 1; }

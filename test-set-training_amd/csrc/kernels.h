@@ -149,6 +149,13 @@ int swiglu_rank_bwd(hipStream_t st, const bf16_t* dact, const bf16_t* gu, bf16_t
 template <typename AT> int logit_rows(hipStream_t st, const float* logits, long ld, const int* target, int n_rows, int V, float* stats, AT* dlogits, long ldd,
                                       float inv_items, const int* opt_ids, int n_opt, float* optl);
 int loss_reduce(hipStream_t st, const float* stats, int n, float inv_items, float* loss_out);
+// attribute.hip -- token attribution (backward seeded with J = sum_i log s(x_i) instead of the training loss).
+// attr_seed: dlogits[r, 0 .. Vp) = d J / d logits of labelled row r (padding exactly 0): row_w[r] (onehot(target) - softmax(z_r)) for row_kind[r] == 0, the same over
+// the option ids only (0 at every other column) for row_kind[r] == 1; stats[r] = {lse, logit[target], option logsumexp, max}. One 256-thread workgroup per row.
+template <typename AT> int attr_seed(hipStream_t st, const float* logits, long ld, const int* target, const float* row_w, const int* row_kind, const int* opt_ids,
+                                     int n_opt, int n_rows, int V, int Vp, float* stats, AT* dlogits, long ldd);
+// token_attr: gxi[t] = sum_c g[t, c] e[t, c], gnorm[t] = sqrt(sum_c g[t, c]^2) for T rows of d columns (a multiple of 8, at most 8192); one wave per token, fp32
+template <typename AT> int token_attr(hipStream_t st, const AT* g, const AT* e, int T, int d, float* gxi, float* gnorm);
 int ids_gather(hipStream_t st, const int* src, int* ids, int n, int n_src);    // ids[i] = src[ids[i]] (device-side batch of a trimmed TST_BATCH_DEVICE_IDS call)
 int ids_check(hipStream_t st, const int* ids, int T, int vocab, int* flag);   // *flag = 1 when an id lies outside [0, vocab)
 template <typename AT> int cast_from_f32(hipStream_t st, const float* in, AT* out, long n, float scale);

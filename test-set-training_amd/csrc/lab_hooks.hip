@@ -237,6 +237,19 @@ int tst_k_logit_rows(const float* logits, int64_t ld, const int32_t* target, int
                      const int32_t* opt_ids, int n_opt, float* optl) {
   return logit_rows(nullptr, logits, ld, target, n_rows, V, stats, (bf16_t*)dlogits, ldd, inv_items, opt_ids, n_opt, optl);
 }
+// token attribution (csrc/attribute.hip): every pointer is a device pointer; the _f32 forms are the strict-mode instances
+int tst_k_attr_seed(const float* logits, int64_t ld, const int32_t* target, const float* row_w, const int32_t* row_kind, const int32_t* opt_ids, int n_opt, int n_rows,
+                    int V, int Vp, float* stats, void* dlogits, int64_t ldd) {
+  return attr_seed<bf16_t>(nullptr, logits, ld, target, row_w, row_kind, opt_ids, n_opt, n_rows, V, Vp, stats, (bf16_t*)dlogits, ldd);
+}
+int tst_k_attr_seed_f32(const float* logits, int64_t ld, const int32_t* target, const float* row_w, const int32_t* row_kind, const int32_t* opt_ids, int n_opt,
+                        int n_rows, int V, int Vp, float* stats, float* dlogits, int64_t ldd) {
+  return attr_seed<float>(nullptr, logits, ld, target, row_w, row_kind, opt_ids, n_opt, n_rows, V, Vp, stats, dlogits, ldd);
+}
+int tst_k_token_attr(const void* g, const void* e, int T, int d, float* gxi, float* gnorm) {
+  return token_attr<bf16_t>(nullptr, (const bf16_t*)g, (const bf16_t*)e, T, d, gxi, gnorm);
+}
+int tst_k_token_attr_f32(const float* g, const float* e, int T, int d, float* gxi, float* gnorm) { return token_attr<float>(nullptr, g, e, T, d, gxi, gnorm); }
 int tst_k_attn_fwd(const void* qkv, int64_t ld, const int32_t* cu, int n_seqs, int max_len, void* out, int64_t ldo, float* lse, int T, int H, int Hkv, int dh,
                    float scale) {
   return attn_fwd(nullptr, (const bf16_t*)qkv, ld, cu, n_seqs, max_len, (bf16_t*)out, ldo, lse, T, H, Hkv, dh, scale);

@@ -91,6 +91,10 @@ def build_parser():
         p.add_argument("--max-new-tokens", type=int, default=8, help="with --generate: tokens generated per sample (1..256)")
         p.add_argument("--eos-ids", default=None, help="with --generate: comma-separated token ids that end an answer; default: eos_token_id of "
                        "<model-dir>/generation_config.json or config.json when present, else none")
+        p.add_argument("--attribute", action="store_true", help="also attribute every held-out sample's score to its prompt tokens (one more forward + backward "
+                       "per held-out batch; include/tst_hip.h tst_attribute_async): the records gain attr = {gxi, gnorm} over the prompt tokens and, with a "
+                       "tokenizer, attr_top. Off: the run is unchanged. Not with --dp > 1 or --layout dp-stacked")
+        p.add_argument("--attribute-top", type=int, default=5, help="with --attribute: tokens listed in attr_top (largest gradient norm first)")
         if name == "prune":
             p.add_argument("--rounds", type=int, default=4)
             p.add_argument("--tau", type=float, default=0.5)
@@ -159,6 +163,12 @@ def parse_eos_ids(a):
 def _args_to_train(a):
     from .trainer import TrainArgs
     gen = dict(generate=True, max_new_tokens=int(a.max_new_tokens), eos_ids=parse_eos_ids(a)) if getattr(a, "generate", False) else {}
+    if getattr(a, "attribute", False):
+        if getattr(a, "dp", 1) > 1 or getattr(a, "layout", None) == "dp-stacked":
+            raise SystemExit("--attribute is not available on the data-parallel layouts (--dp > 1, --layout dp-stacked)")
+        if int(a.attribute_top) < 0:
+            raise SystemExit("--attribute-top must be >= 0")
+        gen.update(attribute=True, attribute_top=int(a.attribute_top))
     return TrainArgs(**gen, learning_rate=a.learning_rate, num_train_epochs=a.num_train_epochs, per_device_train_batch_size=a.per_device_train_batch_size,
                      warmup_steps=a.warmup_steps, weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm, seed=a.seed, lora_r=a.lora_r,
                      lora_alpha=a.lora_alpha, logging_steps=a.logging_steps, gradient_accumulation_steps=max(1, a.gradient_accumulation_steps))

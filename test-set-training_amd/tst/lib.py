@@ -135,6 +135,9 @@ SIGNATURES = {
     "tst_generate_async": (C.c_int, [_P, C.POINTER(Batch), C.c_int32, _P, C.c_int32]),
     "tst_generate_fetch": (C.c_int, [_P, _P, _P, _P]),
     "tst_generate": (C.c_int, [_P, C.POINTER(Batch), C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    "tst_attribute_async": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.c_int32]),
+    "tst_attribute_fetch": (C.c_int, [_P, _P, _P, _P]),
+    "tst_attribute": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.c_int32, _P, _P, _P]),
     "tst_profile_enable": (C.c_int, [_P, _I]),
     "tst_profile_read": (C.c_int, [_P, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_L), _I]),
     "tst_profile_intervals": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _L, C.POINTER(_L)]),
@@ -176,6 +179,10 @@ LAB_SIGNATURES = {
     "tst_k_gelu_bwd": (C.c_int, [_P, _P, _P, _L]),
     "tst_k_embed_pos": (C.c_int, [_P, _P, _P, _P, _P, _I, _I, _I, _I]),
     "tst_k_logit_rows": (C.c_int, [_P, _L, _P, _I, _I, _P, _P, _L, _F, _P, _I, _P]),
+    "tst_k_attr_seed": (C.c_int, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _L]),
+    "tst_k_attr_seed_f32": (C.c_int, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _L]),
+    "tst_k_token_attr": (C.c_int, [_P, _P, _I, _I, _P, _P]),
+    "tst_k_token_attr_f32": (C.c_int, [_P, _P, _I, _I, _P, _P]),
     "tst_k_attn_fwd": (C.c_int, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _I, _F]),
     "tst_k_attn_bwd": (C.c_int, [_P, _L, _P, _L, _P, _L, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _F]),
     "tst_k_attn_fwd_rope": (C.c_int, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _I, _F, _P, _P]),
@@ -212,6 +219,8 @@ HOST_SIGNATURES = {
     "tst_host_plan_batch": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I]),
     "tst_host_plan_generate": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I]),
     "tst_host_cut_at_eos": (C.c_int, [_P, _P, _P, _I, _I, _P, _I]),
+    "tst_host_plan_attribute": (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I]),
+    "tst_host_untrim_tokens": (C.c_int, [_P, _P, _P, _I, _P]),
 }
 
 
@@ -352,6 +361,37 @@ def host_cut_at_eos(tokens, logp, eos_ids):
     if load_host().tst_host_cut_at_eos(_ptr(tok), _ptr(lp), _ptr(nn), tok.shape[0], tok.shape[1], _ptr(eos) if len(eos) else None, len(eos)) != 0:
         raise TstError("tst_host_cut_at_eos: bad arguments")
     return tok, lp, nn
+
+
+def host_plan_attribute(mc, ids, labels, cu, seq_kind=None, option_ids=()):
+    """tsthost::plan_attribute through the CPU library: (row_w, row_kind, row_seq) of the labelled rows; raises TstError with the library's message for a refusal"""
+    L = load_host()
+    ids = np.ascontiguousarray(ids, np.int32)
+    cu = np.ascontiguousarray(cu, np.int32)
+    lab = None if labels is None else np.ascontiguousarray(labels, np.int32)
+    kind = None if seq_kind is None else np.ascontiguousarray(seq_kind, np.int32)
+    opt = np.ascontiguousarray(option_ids, np.int32)
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    b = Batch(ip(ids), ip(lab), ip(cu), len(cu) - 1, len(ids), None, 0)
+    n, cap = C.c_int32(), max(1, len(ids))
+    w, k, q, err = np.zeros(cap, np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.int32), C.create_string_buffer(256)
+    rc = L.tst_host_plan_attribute(C.byref(mc), C.byref(b), None if kind is None else _ptr(kind), _ptr(opt) if len(opt) else None, len(opt), C.byref(n), _ptr(w),
+                                   _ptr(k), _ptr(q), err, 256)
+    if rc != 0:
+        raise TstError(err.value.decode() or f"tst_host_plan_attribute rc={rc}")
+    return w[:n.value], k[:n.value], q[:n.value]
+
+
+def host_untrim_tokens(values, cu_dev, cu_src):
+    """per-token values of the tokens the device ran -> the caller's token order (a trimmed token gets 0), as tst_attribute_fetch does"""
+    src = np.ascontiguousarray(values, np.float32)
+    cd, cs = np.ascontiguousarray(cu_dev, np.int32), np.ascontiguousarray(cu_src, np.int32)
+    if len(cd) != len(cs) or len(cd) < 1 or len(src) < int(cd[-1]):
+        raise TstError("tst_host_untrim_tokens: bad arguments")
+    dst = np.full(max(1, int(cs[-1])), np.nan, np.float32)
+    if load_host().tst_host_untrim_tokens(_ptr(src), _ptr(cd), _ptr(cs), len(cd) - 1, _ptr(dst)) != 0:
+        raise TstError("tst_host_untrim_tokens: bad arguments")
+    return dst[:int(cs[-1])]
 
 
 def device_count():
@@ -855,6 +895,31 @@ class Context:
     def generate(self, ids, cu, max_new_tokens, eos_ids=(), seq_slot=None):
         self.generate_async(ids, cu, max_new_tokens, eos_ids, seq_slot)
         return self.generate_fetch()
+
+    # ---- token attribution (include/tst_hip.h tst_attribute_async)
+    def attribute_async(self, ids, labels, cu, seq_kind=None, option_ids=(), seq_slot=None):
+        """enqueue the input-gradient attribution of log s(x) for the packed batch; seq_kind[i] = 0 (open form: mean log-probability of the labelled tokens) or
+        1 (option form: the one labelled token against option_ids); None = all open. Results come from attribute_fetch()."""
+        b, keep = self._batch(ids, labels, cu, seq_slot)
+        n_opt = len(option_ids)
+        opt_a, _ = _i32(np.asarray(option_ids, np.int32) if n_opt else np.zeros(1, np.int32))
+        kind_a = None if seq_kind is None else np.ascontiguousarray(seq_kind, np.int32)
+        if kind_a is not None and len(kind_a) != len(keep[2]) - 1:
+            raise TstError("seq_kind needs one entry per sequence")
+        self._check(self.lib.tst_attribute_async(self.h, C.byref(b), None if kind_a is None else _ptr(kind_a), _ptr(opt_a), n_opt), "tst_attribute_async")
+        self._pending_attr = (len(keep[0]), len(keep[2]) - 1)
+
+    def attribute_fetch(self):
+        """(gxi [n_tokens], gnorm [n_tokens], log_s [n_seqs]): gradient x input and gradient norm of every token's embedding output, in the caller's token order"""
+        n_tok, n_seq = getattr(self, "_pending_attr", None) or (1, 1)
+        gxi, gnorm, logs = np.zeros(n_tok, np.float32), np.zeros(n_tok, np.float32), np.zeros(n_seq, np.float32)
+        self._check(self.lib.tst_attribute_fetch(self.h, _ptr(gxi), _ptr(gnorm), _ptr(logs)), "tst_attribute_fetch")
+        self._pending_attr = None
+        return gxi, gnorm, logs
+
+    def attribute(self, ids, labels, cu, seq_kind=None, option_ids=(), seq_slot=None):
+        self.attribute_async(ids, labels, cu, seq_kind, option_ids, seq_slot)
+        return self.attribute_fetch()
 
     def forward_logits(self, ids, cu, rows, seq_slot=None):
         b, keep = self._batch(ids, None, cu, seq_slot)

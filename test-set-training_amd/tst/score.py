@@ -6,6 +6,10 @@ only names s(x), so the definition is this build's and is frozen here):
   * numeric / open answer (1..4 tokens): s(x) = exp(mean_t log p(answer_t | prefix)), teacher-forced;
     correct iff every answer token is the arg-max token.
 
+With attribution switched on (TrainArgs.attribute) a sample also carries WHICH prompt tokens its score rests on: the gradient of log s(x) with respect to every
+prompt token's embedding output, as gradient x input and as gradient norm (token_attribution; the definition is frozen in include/tst_hip.h
+tst_attribute_async). log s is differentiated rather than s so that the scale does not collapse for confident samples; d s = s d log s.
+
 With generation switched on (TrainArgs.generate) a sample also carries what the text-only model SAYS: its greedy continuation of the prompt
 (generated_answers), and gen_correct = that continuation starts with the reference answer's tokens. bias_scores does not change.
 """
@@ -35,6 +39,26 @@ def bias_scores(samples, logp, correct_rows, opt_logits, row_seq):
             s[i] = np.exp(np.mean(logp[rows].astype(np.float64)))
             correct[i] = int(correct_rows[rows].all())
     return s, pred, correct
+
+
+def attribution_kinds(samples):
+    """seq_kind of Context.attribute for the samples of a batch: 1 (option form) for multiple-choice samples, 0 (open form) otherwise"""
+    return np.array([1 if s.kind == "mca" else 0 for s in samples], np.int32)
+
+
+def token_attribution(samples, gxi, gnorm, logs):
+    """samples: the attributed batch in batch order (full sequences, as data.collate packs them); gxi / gnorm per token and logs per sample as returned by
+    Context.attribute. Returns per sample dict(gxi, gnorm: the prompt tokens' values, share: gnorm / sum of gnorm over the prompt, log_s)."""
+    gxi, gnorm = np.asarray(gxi, np.float32), np.asarray(gnorm, np.float32)
+    if len(gxi) != sum(len(s.ids) for s in samples) or len(gnorm) != len(gxi) or len(logs) != len(samples):
+        raise ValueError("token_attribution: the arrays do not belong to this batch")
+    out, o = [], 0
+    for i, smp in enumerate(samples):
+        g, n = gxi[o:o + smp.n_prompt].copy(), gnorm[o:o + smp.n_prompt].copy()
+        tot = float(n.astype(np.float64).sum())
+        out.append(dict(gxi=g, gnorm=n, share=(n / tot if tot > 0 else np.zeros_like(n)).astype(np.float32), log_s=float(logs[i])))
+        o += len(smp.ids)
+    return out
 
 
 def generated_answers(samples, tokens, n_new, eos_ids=()):

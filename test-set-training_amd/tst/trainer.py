@@ -6,7 +6,7 @@ AdamW 0.9/0.999/1e-8, wd 0, max_grad_norm 1.0, 3 epochs, seed 42) so a future up
 batch of 16 is the value BASELINE.md fixes for the metric."""
 import os
 import time
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 
 import numpy as np
 
@@ -38,6 +38,15 @@ class TrainArgs:
     generate: bool = False
     max_new_tokens: int = 8
     eos_ids: tuple = ()
+    # token attribution on the held-out fold (off by default): every record gains `attr`, the gradient of log s(x) per prompt token as gradient x input and
+    # gradient norm (include/tst_hip.h tst_attribute_async), and with a tokenizer `attr_top`. The two settings are constructor arguments and attributes but NOT
+    # dataclass fields: dataclasses.asdict(args) -- what the run fingerprint of a run without attribution hashes -- lists exactly the fields it always listed, so
+    # such a run's directory still resumes; tst.diagnose.run_fingerprint adds them when attribution is on. (dataclasses.replace does not carry them over.)
+    attribute: InitVar[bool] = False
+    attribute_top: InitVar[int] = 5
+
+    def __post_init__(self, attribute, attribute_top):
+        self.attribute, self.attribute_top = bool(attribute), int(attribute_top)
 
 
 def linear_lr(step, total, lr0, warmup=0):
@@ -275,6 +284,82 @@ def generate_heldout_stacked(ctxs, sample_sets, args: TrainArgs):
                 ids, cu = collate_prompts([x for _, _, xs in parts for x in xs])
                 seq_slot = np.concatenate([np.full(len(xs), sl, np.int32) for sl, _, xs in parts])
                 c.generate_async(ids, cu, args.max_new_tokens, args.eos_ids, seq_slot)
+                pending[j] = [(i, xs) for _, i, xs in parts]
+    for j in range(len(ctxs)):
+        fetch(j)
+    return outs
+
+
+# ---------------------------------------------------------------------------------------------- token attribution of the held-out fold
+def _attribute_async(ctx, batch, args: TrainArgs, seq_slot=None):
+    ids, labels, cu = D.collate(batch)
+    ctx.attribute_async(ids, labels, cu, S.attribution_kinds(batch), args.option_ids, seq_slot)   # MCA and open samples in one batch
+
+
+def attribute_heldout(ctx, samples, args: TrainArgs):
+    """input-gradient attribution of log s(x) for every held-out sample (Context.attribute, batches of per_device_eval_batch_size); returns
+    tst.score.token_attribution's dict per sample in input order. About one training forward + backward per batch."""
+    bs = args.per_device_eval_batch_size
+    out = []
+    for b in range(0, len(samples), bs):
+        batch = samples[b:b + bs]
+        _attribute_async(ctx, batch, args)
+        out += S.token_attribution(batch, *ctx.attribute_fetch())
+    return out
+
+
+def attribute_heldout_concurrent(ctxs, sample_sets, args: TrainArgs):
+    """attribute_heldout for several resident folds: batch b of every fold is enqueued before batch b-1's results are read."""
+    bs = args.per_device_eval_batch_size
+    outs = [[] for _ in ctxs]
+    pending = [None] * len(ctxs)
+
+    def fetch(j):
+        if pending[j] is not None:
+            outs[j] += S.token_attribution(pending[j], *ctxs[j].attribute_fetch())
+            pending[j] = None
+
+    nb = max((len(smp) + bs - 1) // bs for smp in sample_sets) if sample_sets else 0
+    for b in range(nb):
+        for j, (c, smp) in enumerate(zip(ctxs, sample_sets)):
+            fetch(j)
+            batch = smp[b * bs:(b + 1) * bs]
+            if batch:
+                _attribute_async(c, batch, args)
+                pending[j] = batch
+    for j in range(len(ctxs)):
+        fetch(j)
+    return outs
+
+
+def attribute_heldout_stacked(ctxs, sample_sets, args: TrainArgs):
+    """attribute_heldout on stacked contexts: batch b of all folds of a context is one attribution, every sequence under its own slot's adapters;
+    returns the per-sample dicts per fold, in the order of sample_sets."""
+    where = place_folds(len(sample_sets), ctxs)
+    bs = args.per_device_eval_batch_size
+    outs = [[] for _ in sample_sets]
+    pending = [None] * len(ctxs)
+    mine = [[(sl, i) for i, (jj, sl) in enumerate(where) if jj == j] for j in range(len(ctxs))]
+
+    def fetch(j):
+        if pending[j] is not None:
+            parts = pending[j]   # [(fold position, samples)]
+            got = S.token_attribution([x for _, b in parts for x in b], *ctxs[j].attribute_fetch())
+            o = 0
+            for i, b in parts:
+                outs[i] += got[o:o + len(b)]
+                o += len(b)
+            pending[j] = None
+
+    nb = max((len(smp) + bs - 1) // bs for smp in sample_sets) if sample_sets else 0
+    for b in range(nb):
+        for j, c in enumerate(ctxs):
+            fetch(j)
+            parts = [(sl, i, sample_sets[i][b * bs:(b + 1) * bs]) for sl, i in mine[j]]
+            parts = [(sl, i, x) for sl, i, x in parts if x]
+            if parts:
+                seq_slot = np.concatenate([np.full(len(xs), sl, np.int32) for sl, _, xs in parts])
+                _attribute_async(c, [x for _, _, xs in parts for x in xs], args, seq_slot)
                 pending[j] = [(i, xs) for _, i, xs in parts]
     for j in range(len(ctxs)):
         fetch(j)

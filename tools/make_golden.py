@@ -8,6 +8,7 @@ It never travels to the GPU box as a dependency: tests read the .npz files.
 
     python tools/make_golden.py            # rewrites tests/golden/*.npz
     python tools/make_golden.py qwen3      # one family only (here: the Qwen3 fixtures, tests/qwen3_inputs.py)
+    python tools/make_golden.py attr       # the token-attribution fixtures (tests/attribution_inputs.py)
 """
 import os
 import sys
@@ -568,6 +569,112 @@ def run_rope_scaling():
     print("rope_scaling:", {k: v.shape for k, v in res.items() if k.endswith("inv_freq")})
 
 
+# ------------------------------------------------------------------------------------------------ token attribution (include/tst_hip.h tst_attribute_async)
+def _inject_lora_any(cfg, m, lora):
+    if cfg.get("arch") != "gpt2":
+        return inject_lora(m, lora, GI.LORA_R, GI.LORA_ALPHA)
+    for p in m.parameters():
+        p.requires_grad_(False)
+    for l, blk in enumerate(m.transformer.h):
+        for mod in GI.GPT2_MODS:
+            parent, leaf, key = getattr(blk, mod.split(".")[0]), mod.split(".")[1], f"layers.{l}.{mod}"
+            setattr(parent, leaf, LoraConv1D(getattr(parent, leaf), lora[key + ".lora_A"], lora[key + ".lora_B"], GI.LORA_ALPHA / GI.LORA_R))
+
+
+def run_attr(tag):
+    """attr_<tag>.npz: gradient x input and gradient norm of J = sum_i log s(x_i) w.r.t. the embedding-layer output, from the HF model fed inputs_embeds with
+    requires_grad. Per fixture set (AI.SETS) and adapter set (AI.ADAPTERS): ref_* from model.double(), hf32_* / hf_bf16_* from model.float() / .bfloat16(),
+    floor32 / floor16 = per output the max over sequences of max_t |x - ref| / max_t |ref|. Sequences run one at a time: they do not interact."""
+    import attribution_inputs as AI
+    cfg, make_w = AI.TAGS[tag]
+    gpt2 = cfg.get("arch") == "gpt2"
+    w = make_w(cfg)
+    ids, labels, cu = AI.batch(tag)
+    opt = torch.from_numpy(AI.option_ids(tag).astype(np.int64))
+    S = len(cu) - 1
+
+    def model(adapter, dtype):
+        m = (hf_gpt2 if gpt2 else hf_model)(cfg, w)
+        if adapter is not None:
+            _inject_lora_any(cfg, m, AI.lora(tag, adapter))
+        for p in m.parameters():
+            p.requires_grad_(False)
+        if dtype == torch.float64:
+            # HF's eager attention takes its softmax in fp32 whatever the model's dtype (modeling_llama.py eager_attention_forward), which would leave the
+            # "fp64" reference with 1e-7 of noise in J; the sdpa path stays in the tensors' dtype. The fp32 / bf16 runs keep the eager path of every other fixture.
+            m.config._attn_implementation = "sdpa"
+            # likewise HF's RMSNorm modules (layer norms, Qwen3 head norms) run in fp32 whatever they are given (modeling_llama.py LlamaRMSNorm.forward): the
+            # reference model takes the same formula in its own dtype
+            for mod in m.modules():
+                if type(mod).__name__.endswith("RMSNorm"):
+                    mod.forward = (lambda x, mod=mod: mod.weight * (x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + mod.variance_epsilon)))
+        return m.to(dtype).eval()
+
+    def J_of(m, x, lab, kind):
+        z = m(inputs_embeds=x[None]).logits[0].to(torch.float64 if x.dtype == torch.float64 else torch.float32)
+        rows = [p for p in range(len(lab) - 1) if lab[p + 1] != -100]
+        tg = torch.tensor([int(lab[p + 1]) for p in rows])
+        zr = z[rows]
+        if kind == 1:
+            assert len(rows) == 1 and int(tg[0]) in opt.tolist()
+            return zr[0, tg[0]] - torch.logsumexp(zr[0, opt], 0)
+        return torch.log_softmax(zr, -1)[torch.arange(len(rows)), tg].mean()
+
+    def embed_parts(m, s):
+        t = torch.from_numpy(ids[cu[s]:cu[s + 1]].astype(np.int64))
+        if gpt2:
+            return m.transformer.wte.weight[t].detach().clone(), m.transformer.wpe.weight[: len(t)].detach().clone()
+        return m.model.embed_tokens.weight[t].detach().clone(), None
+
+    def attribute(m, kinds):
+        gxi, gnorm, logs = [], [], []
+        for s in range(S):
+            x, pos = embed_parts(m, s)
+            x.requires_grad_(True)
+            J = J_of(m, x, labels[cu[s]:cu[s + 1]], kinds[s])
+            g, = torch.autograd.grad(J, x)
+            e = (x.detach() + pos) if gpt2 else x.detach()   # the embedding-layer output: d J / d e = d J / d x
+            gxi.append((g.double() * e.double()).sum(-1).numpy())
+            gnorm.append(g.double().norm(dim=-1).numpy())
+            logs.append(float(J.detach()))
+        return np.concatenate(gxi), np.concatenate(gnorm), np.array(logs)
+
+    res = dict(option_ids=AI.option_ids(tag))
+    for aname, adapter in AI.ADAPTERS.items():
+        m64, m32, m16 = model(adapter, torch.float64), model(adapter, torch.float32), model(adapter, torch.bfloat16)
+        for sname, kinds in AI.SETS.items():
+            key = f"{sname}/{aname}/"
+            ref = attribute(m64, kinds)
+            # the reference against a central difference of J in fp64: scaling token t's embedding output by 1 +- h moves J by +- h gxi[t]
+            h, worst = 1e-4, 0.0
+            for s, t in ((0, 2), (1, 17), (S - 1, 50)):
+                x, pos = embed_parts(m64, s)
+                e = x + pos if gpt2 else x
+                Jpm = []
+                for sign in (1.0, -1.0):
+                    e2 = e.clone()
+                    e2[t] = e[t] * (1.0 + sign * h)
+                    with torch.no_grad():
+                        Jpm.append(float(J_of(m64, e2 - pos if gpt2 else e2, labels[cu[s]:cu[s + 1]], kinds[s])))
+                fd = (Jpm[0] - Jpm[1]) / (2 * h)
+                worst = max(worst, abs(fd - ref[0][cu[s] + t]) / np.abs(ref[0][cu[s]:cu[s + 1]]).max())
+            if worst > 1e-6:
+                raise SystemExit(f"attr_{tag} {key}: the reference disagrees with the central difference of J ({worst:.3e} relative): nothing written")
+            res[key + "fd_check"] = np.float64(worst)
+            res[key + "ref_gxi"], res[key + "ref_gnorm"], res[key + "ref_logs"] = ref
+            for pre, m in (("hf32", m32), ("hf_bf16", m16)):
+                got = attribute(m, kinds)
+                res[key + pre + "_gxi"], res[key + pre + "_gnorm"], res[key + pre + "_logs"] = got
+                res[key + ("floor32" if pre == "hf32" else "floor16")] = np.array([AI.seq_dev(got[i], ref[i], cu).max() for i in range(2)])
+            print(f"attr_{tag} {key}: fd {worst:.2e} floor32 {res[key + 'floor32']} floor16 {res[key + 'floor16']} logs {np.round(ref[2], 4)}")
+    # the stacked test tells the two adapter sets apart: per set, output and sequence, the distance of the l7 reference from the l99 one
+    for sname in AI.SETS:
+        res[f"{sname}/l99_vs_l7"] = np.stack([AI.seq_dev(res[f"{sname}/l7/ref_{o}"], res[f"{sname}/l99/ref_{o}"], cu) for o in AI.OUTPUTS])
+        f16 = np.maximum(res[f"{sname}/l99/floor16"], res[f"{sname}/l7/floor16"])
+        print(f"attr_{tag} {sname}: l99 vs l7 per output x sequence\n{res[f'{sname}/l99_vs_l7']}\n  4 x floor16 = {4 * f16}")
+    np.savez_compressed(os.path.join(OUT, f"attr_{tag}.npz"), **res)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = set(sys.argv[1:]) or {"ops", "kfold", "llama", "gpt2", "strict"}   # e.g. `python tools/make_golden.py gpt2` regenerates only that family
@@ -592,6 +699,9 @@ if __name__ == "__main__":
     if "accum" in which:
         for tag, cfg in (("tiny", GI.TINY_CFG), ("tiny2", GI.TINY2_CFG), ("gpt2", GI.GPT2_CFG)):
             run_accum(cfg, tag)
+    if "attr" in which:   # the token-attribution fixtures only (attr_<tag>.npz, tests/attribution_inputs.py): not part of the default set
+        for tag in ("tiny", "tiny2", "qwen", "qwen3", "gpt2"):
+            run_attr(tag)
     if "rope" in which or "strict" in which:
         run_rope_scaling()
         run_strict(GI.TINY_RS_CFG, "tiny_rs")
