@@ -390,6 +390,32 @@ int tst_attribute_fetch(tst_ctx* ctx, float* gxi_out /* [n_tokens] */, float* gn
 int tst_attribute(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_kind, const int32_t* option_ids, int32_t n_opt, float* gxi_out, float* gnorm_out,
                   float* logs_out);
 
+/* ---- token attribution: integrated gradients of log s(x) along a baseline path ----
+ * J_i, seq_kind, option_ids and the embedding-layer output e[t, :] are those of tst_attribute_async. baseline_ids[n_tokens] (HOST memory, like labels, also for a
+ * TST_BATCH_DEVICE_IDS batch; one id per token of the caller's batch) names the baseline prompt: b[t, :] = embed_tokens[baseline_ids[t]] (GPT-2:
+ * wte[baseline_ids[t]] + wpe[pos], so the position term cancels in e - b). There is no zero-vector baseline: on RMSNorm models the first norm is scale-invariant down
+ * to eps and the integrand is singular at the origin. A token with baseline_ids[t] == input_ids[t] is not interpolated; its result is exactly 0.
+ * For n_steps = m the path is sampled by the midpoint rule, alpha_k = (k - 1/2) / m, x_k = b + alpha_k (e - b) -- evaluated in fp32 as written and
+ * rounded once to the activation type -- and with g_k = d (sum_i J_i) / d x at x_k the call returns
+ *   ig_out[t]        = (1 / m) sum_{k = 1 .. m} sum_d g_k[t, d] (e - b)[t, d]      (signed; fp32 accumulation, k ascending: bit-reproducible)
+ *   logs_out[i]      = J_i(e)     (what tst_attribute returns as logs_out)
+ *   logs_base_out[i] = J_i(b)
+ * in the caller's token order (a token "trim_last_token" keeps off the device gets 0). Completeness is the contract a reader can use: the ig of the tokens of
+ * sequence i sum to logs_out[i] - logs_base_out[i] as m grows; at a fixed m the sum is a quantity of its own and the gap is the quadrature error.
+ * tst_attribute_ig_async enqueues everything at once -- a forward + head pass at the baseline, one at the real prompt, then m times interpolation, forward, head,
+ * backward to the embedding output and the per-token reduction -- without a host wait in between; tst_attribute_ig_fetch waits for that work only.
+ * Availability, side effects (the flat gradient is UNSPECIFIED afterwards; an optimizer step on it returns TST_ESTATE) and the TST_ESTATE cases are those of
+ * tst_attribute_async. ONE attribution of either kind may be pending per context; a fetch of the other kind returns TST_ESTATE and leaves the pending one pending.
+ * Its buffers (8 bytes per max_tokens on the device, besides tst_attribute_async's own; pinned staging) are allocated by the first call and counted in
+ * tst_device_bytes. TST_EINVAL before anything is allocated or launched: the cases of tst_attribute_async, baseline_ids == NULL, a baseline id outside the vocabulary,
+ * n_steps outside 1 .. TST_IG_MAX_STEPS. */
+#define TST_IG_MAX_STEPS 256
+int tst_attribute_ig_async(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_kind /* [n_seqs] or NULL */, const int32_t* option_ids, int32_t n_opt,
+                           const int32_t* baseline_ids /* [n_tokens], host */, int32_t n_steps);
+int tst_attribute_ig_fetch(tst_ctx* ctx, float* ig_out /* [n_tokens] */, float* logs_out /* [n_seqs] */, float* logs_base_out /* [n_seqs] */);
+int tst_attribute_ig(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_kind, const int32_t* option_ids, int32_t n_opt, const int32_t* baseline_ids, int32_t n_steps,
+                     float* ig_out, float* logs_out, float* logs_base_out);
+
 /* ---- measurement hooks (bench.py): HIP events on the ctx stream around the dominant kernel class ---- */
 /* on: bit 0 = bracket every dense contraction launch with HIP events on its stream; bit 1 = also bracket the HBM-bound kernel classes
  * (variant ids 101 AdamW, 102 SwiGLU, 103 RMSNorm / LayerNorm, 104 attention); 0 = off */

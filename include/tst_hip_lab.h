@@ -103,6 +103,18 @@ int tst_k_attr_seed_f32(const float* logits, int64_t ld, const int32_t* target, 
                         int n_rows, int V, int Vp, float* stats, float* dlogits, int64_t ldd);
 int tst_k_token_attr(const void* g, const void* e, int T, int d, float* gxi, float* gnorm);
 int tst_k_token_attr_f32(const float* g, const float* e, int T, int d, float* gxi, float* gnorm);
+/* integrated-gradients kernels (csrc/attribute.hip). embed_interp: out[t, 0 .. d) = b + alpha (e - b), e = E[ids[t]], b = E[bids[t]] (+ P[pos[t]] when P != NULL; pos and npos
+ * are ignored otherwise), the difference, the product and each sum rounded to fp32, ONE rounding to the element type; 0 <= alpha <= 1, d % 8 == 0, ids clamped into [0, vocab).
+ * alpha == 1 copies E[ids[t]] (what tst_k_embed writes; with P, what tst_k_embed_pos writes), alpha == 0 copies E[bids[t]], and a token with bids[t] == ids[t] gets
+ * its table row at every alpha, all bit for bit.
+ * token_ig: acc[t] = (first ? 0 : acc[t]) + w sum_c g[t, c] (E[ids[t], c] - E[bids[t], c]), the difference in fp32; exactly (first ? 0 : acc[t]) + 0 for a token
+ * with bids[t] == ids[t]. fp32 accumulation in token_attr's order, bit-reproducible. */
+int tst_k_embed_interp(const int32_t* ids, const int32_t* bids, const int32_t* pos, const void* E, const void* P, void* out, int T, int d, int vocab, int npos,
+                       float alpha);
+int tst_k_embed_interp_f32(const int32_t* ids, const int32_t* bids, const int32_t* pos, const float* E, const float* P, float* out, int T, int d, int vocab, int npos,
+                           float alpha);
+int tst_k_token_ig(const void* g, const void* E, const int32_t* ids, const int32_t* bids, int T, int d, int vocab, float w, int first, float* acc);
+int tst_k_token_ig_f32(const float* g, const float* E, const int32_t* ids, const int32_t* bids, int T, int d, int vocab, float w, int first, float* acc);
 int tst_k_attn_fwd(const void* qkv, int64_t ld, const int32_t* cu, int n_seqs, int max_len, void* out, int64_t ldo, float* lse, int T, int H,
                    int Hkv, int dh, float scale);
 int tst_k_attn_bwd(const void* qkv, int64_t ld, const void* out, int64_t ldo, const void* dO, int64_t lddo, const float* lse, float* delta,

@@ -55,6 +55,12 @@ int tst_host_plan_attribute(const tst_model_cfg* cfg, const tst_batch* b, const 
 /* the fetch side of an attribution: per-token values of the tokens the device ran (sequence s at [cu_dev[s], cu_dev[s + 1])) into the caller's token order
  * (sequence s at [cu_src[s], cu_src[s + 1])); a token the device did not run (trim_last_token) gets 0. TST_EINVAL when a sequence is longer on the device. */
 int tst_host_untrim_tokens(const float* src, const int32_t* cu_dev, const int32_t* cu_src, int n_seqs, float* dst);
+/* tsthost::plan_ig (integrated gradients, include/tst_hip.h tst_attribute_ig_async): the checks the call adds to tst_host_plan_attribute's -- baseline_ids (one per
+ * token of the caller's batch, inside the vocabulary) and n_steps (1 .. TST_IG_MAX_STEPS). alpha_out, when not NULL, receives the n_steps midpoints
+ * (k - 1/2) / n_steps in fp32 as the engine passes them to its kernels. err_out / err_cap receive the message of a refusal. Returns TST_OK or TST_EINVAL. */
+int tst_host_plan_ig(const tst_model_cfg* cfg, const tst_batch* b, const int32_t* baseline_ids, int n_steps, float* alpha_out, char* err_out, int err_cap);
+/* the upload side: per-token ids of the caller's batch into the order the device runs them (the inverse of tst_host_untrim_tokens; a trimmed token is dropped) */
+int tst_host_trim_tokens(const int32_t* src, const int32_t* cu_dev, const int32_t* cu_src, int n_seqs, int32_t* dst);
 
 #if defined(__GNUC__)
 #pragma GCC visibility pop

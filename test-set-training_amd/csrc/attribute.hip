@@ -1,7 +1,10 @@
 // Token attribution (include/tst_hip.h tst_attribute_async): the two kernels a backward pass seeded with J = sum_i log s(x_i) adds to the training one.
 //   attr_seed   d J / d logits of the labelled rows, in place of logit_rows + loss_reduce (whose seed is the training loss)
 //   token_attr  per token, gradient x input and the gradient's 2-norm of the embedding-layer output
-// Both are HBM-trivial beside the contractions between them; neither uses atomics, so two runs agree bit for bit.
+// and the two that integrated gradients (tst_attribute_ig_async) add to those:
+//   embed_interp  the embedding-layer output on the straight path from a baseline prompt to the real one
+//   token_ig      per token, one term of the path's Riemann sum, accumulated over the steps
+// All are HBM-trivial beside the contractions between them; none uses atomics, so two runs agree bit for bit.
 #include "common.h"
 #include "kernels.h"
 
@@ -121,6 +124,95 @@ __global__ __launch_bounds__(256) void token_attr_kernel(const AT* __restrict__ 
   }
 }
 
+// Integrated gradients, the path: one wave per token t, x[t, :] = b + alpha (e - b) with e = E[ids[t]] and b = E[bids[t]] (ids clamped as the embedding kernels
+// clamp them), evaluated in fp32 as written -- the difference, its product with alpha and the sum, each rounded to fp32, no contraction -- and rounded ONCE to the
+// activation type. The ends, and a token whose baseline is its own id, take no arithmetic at all: the table row is copied (alpha == 1: E[ids[t]], what embed_fwd
+// writes; alpha == 0: E[bids[t]]) -- fp32 would lose e against a b many binades larger, and a -0 of the table stays -0. GPT-2 (P != nullptr) adds P[pos[t]] in fp32
+// before the one rounding, like embed_pos_fwd. The row choice is uniform over the wave.
+template <typename AT>
+__global__ __launch_bounds__(256) void embed_interp_kernel(const int* __restrict__ ids, const int* __restrict__ bids, const int* __restrict__ pos,
+                                                           const AT* __restrict__ E, const AT* __restrict__ P, AT* __restrict__ out, int T, int d, int vocab,
+                                                           int npos, float alpha) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;
+  int id = ids[t], bid = bids[t];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  bid = bid < 0 ? 0 : (bid >= vocab ? vocab - 1 : bid);
+  const AT* er = E + (long)id * d;
+  const AT* br = E + (long)bid * d;
+  const AT* one = (id == bid || alpha == 1.0f) ? er : (alpha == 0.0f ? br : nullptr);   // the row that is the result as it stands
+  const AT* pr = nullptr;
+  if (P) {
+    int p = pos[t];
+    p = p < 0 ? 0 : (p >= npos ? npos - 1 : p);
+    pr = P + (long)p * d;
+  }
+  AT* orow = out + (long)t * d;
+  for (int c = lane * 8; c < d; c += 512) {
+#pragma clang fp contract(off)   // every product and sum below is rounded to fp32 on its own: no fused multiply-add
+    if (one && !pr) {   // a plain gather: bits, not values
+      if constexpr (sizeof(AT) == 2) {
+        *(uint4*)(orow + c) = *(const uint4*)(one + c);
+      } else {
+        *(uint4*)(orow + c) = *(const uint4*)(one + c);
+        *(uint4*)(orow + c + 4) = *(const uint4*)(one + c + 4);
+      }
+      continue;
+    }
+    float a[8];
+    if (one) ld8(one + c, a);
+    else {
+      float b[8];
+      ld8(er + c, a);
+      ld8(br + c, b);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) a[j] = b[j] + alpha * (a[j] - b[j]);
+    }
+    if (pr) {
+      float q[8];
+      ld8(pr + c, q);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) a[j] = a[j] + q[j];
+    }
+    st8(orow + c, a);
+  }
+}
+
+// Integrated gradients, one step of the sum: one wave per token t, v = w sum_c g[t, c] (E[ids[t], c] - E[bids[t], c]), the difference taken in fp32 from the
+// table rows (GPT-2's position term cancels in it); acc[t] = v when `first`, acc[t] + v otherwise -- the caller's steps run in stream order, so the adds happen in
+// that order and the sum is bit-reproducible. A token whose baseline is its own id gets exactly 0 without reading g. Same summation order as token_attr.
+template <typename AT>
+__global__ __launch_bounds__(256) void token_ig_kernel(const AT* __restrict__ g, const AT* __restrict__ E, const int* __restrict__ ids, const int* __restrict__ bids,
+                                                       int T, int d, int vocab, float w, int first, float* __restrict__ acc) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;   // (whole waves leave: the shuffles below run on full waves)
+  int id = ids[t], bid = bids[t];
+  id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  bid = bid < 0 ? 0 : (bid >= vocab ? vocab - 1 : bid);
+  float dot = 0.f;
+  if (id != bid) {   // (uniform over the wave)
+    const AT* gr = g + (long)t * d;
+    const AT* er = E + (long)id * d;
+    const AT* br = E + (long)bid * d;
+    for (int c = lane * 8; c < d; c += 512) {
+      float a[8], e[8], b[8];
+      ld8(gr + c, a);
+      ld8(er + c, e);
+      ld8(br + c, b);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) dot = fmaf(a[j], e[j] - b[j], dot);
+    }
+    dot = wave_sum(dot);
+  }
+  if (lane == 0) {
+#pragma clang fp contract(off)   // w dot is rounded before it is added: the sum over the steps is the fp32 sum of the steps' own results
+    const float v = w * dot;
+    acc[t] = first ? v : acc[t] + v;
+  }
+}
+
 template <typename AT>
 int attr_seed(hipStream_t st, const float* logits, long ld, const int* target, const float* row_w, const int* row_kind, const int* opt_ids, int n_opt, int n_rows,
               int V, int Vp, float* stats, AT* dlogits, long ldd) {
@@ -139,9 +231,27 @@ int token_attr(hipStream_t st, const AT* g, const AT* e, int T, int d, float* gx
   return hipGetLastError() == hipSuccess ? TST_OK : TST_EHIP;
 }
 
+template <typename AT>
+int embed_interp(hipStream_t st, const int* ids, const int* bids, const int* pos, const AT* E, const AT* P, AT* out, int T, int d, int vocab, int npos, float alpha) {
+  if (T <= 0) return TST_OK;
+  if (!ids || !bids || !E || !out || d <= 0 || (d & 7) || vocab <= 0 || (P && (!pos || npos <= 0)) || !(alpha >= 0.0f && alpha <= 1.0f)) return TST_EINVAL;
+  hipLaunchKernelGGL(embed_interp_kernel<AT>, dim3(tst_ceil_div(T, 4)), dim3(256), 0, st, ids, bids, pos, E, P, out, T, d, vocab, npos, alpha);
+  return hipGetLastError() == hipSuccess ? TST_OK : TST_EHIP;
+}
+
+template <typename AT>
+int token_ig(hipStream_t st, const AT* g, const AT* E, const int* ids, const int* bids, int T, int d, int vocab, float w, bool first, float* acc) {
+  if (T <= 0) return TST_OK;
+  if (!g || !E || !ids || !bids || !acc || d <= 0 || (d & 7) || vocab <= 0) return TST_EINVAL;
+  hipLaunchKernelGGL(token_ig_kernel<AT>, dim3(tst_ceil_div(T, 4)), dim3(256), 0, st, g, E, ids, bids, T, d, vocab, w, first ? 1 : 0, acc);
+  return hipGetLastError() == hipSuccess ? TST_OK : TST_EHIP;
+}
+
 #define INSTANTIATE(AT)                                                                                                                                  \
   template int attr_seed<AT>(hipStream_t, const float*, long, const int*, const float*, const int*, const int*, int, int, int, int, float*, AT*, long); \
-  template int token_attr<AT>(hipStream_t, const AT*, const AT*, int, int, float*, float*);
+  template int token_attr<AT>(hipStream_t, const AT*, const AT*, int, int, float*, float*);                                                            \
+  template int embed_interp<AT>(hipStream_t, const int*, const int*, const int*, const AT*, const AT*, AT*, int, int, int, int, float);                \
+  template int token_ig<AT>(hipStream_t, const AT*, const AT*, const int*, const int*, int, int, int, float, bool, float*);
 INSTANTIATE(bf16_t)
 INSTANTIATE(float)
 #undef INSTANTIATE

@@ -27,6 +27,7 @@
 #include "kernels.h"
 
 static_assert(tsthost::kMaxStack == TST_MAX_STACK, "host_logic.h and kernels.h disagree about the stack size");
+static_assert(tsthost::kIgMaxSteps == TST_IG_MAX_STEPS, "host_logic.h and tst_hip.h disagree about the step limit of integrated gradients");
 
 namespace {
 
@@ -306,6 +307,14 @@ struct tst_ctx {
   bool attr_pass = false, grad_stale = false;
   tsthost::AttrPlan attr_plan;
   std::vector<int> attr_cu_dev, attr_cu_src;
+  // Integrated gradients (tst_attribute_ig_async): the same pending slot as an attribution, attr_ig telling the two kinds apart. Allocated by the first such call of
+  // the context. ig_dev = baseline ids in device token order [Tmax] | ig [Tmax] (4-byte words); h_ig = the pinned staging of the baseline ids [Tmax], then ig [Tmax] |
+  // row statistics at the baseline [Rmax * 4] | at the real prompt [Rmax * 4] of the pending call. ig_on: forward() writes layer 0's input with embed_interp at
+  // ig_alpha instead of the embedding gather (set around the passes of tst_attribute_ig_async only).
+  float* ig_dev = nullptr;
+  float* h_ig = nullptr;
+  bool attr_ig = false, ig_on = false;
+  float ig_alpha = 1.0f;
   float* d_loss = nullptr;
   int cur_T = 0, cur_S = 0, cur_R = 0, cur_maxlen = 0, cur_items = 0;
   double cur_sumsq_len = 0;   // sum over the batch's sequences of length^2 (attention work)
@@ -1055,7 +1064,10 @@ int forward(CtxT<AT>* ctx, bool stash, GenPass gen = {}) {
   ctx->lc_used = ctx->lc_on && ctx->lc_batch_ok && ctx->cur_R > 0 && 2 * ctx->cur_R <= T;
   whatif_tick();   // (process-wide: the bench's contexts step in turn)
   CTX_RC(opt_need(ctx, 1));   // norm vectors / biases and the embedding side of a pending optimizer step
-  if (ctx->gpt2) CTX_RC(embed_pos_fwd<AT>(st, ctx->d_ids, ctx->d_pos, ctx->embed, ctx->wpe, L0.x_in, T, d, ctx->V, ctx->npos));
+  // (an integrated-gradients pass enters the stack on the path from the baseline prompt's embeddings to the real ones; everything behind the embedding is unchanged)
+  if (ctx->ig_on) CTX_RC(embed_interp<AT>(st, ctx->d_ids, (const int*)ctx->ig_dev, ctx->d_pos, ctx->embed, ctx->gpt2 ? ctx->wpe : (const AT*)nullptr, L0.x_in, T, d, ctx->V,
+                                         ctx->npos, ctx->ig_alpha));
+  else if (ctx->gpt2) CTX_RC(embed_pos_fwd<AT>(st, ctx->d_ids, ctx->d_pos, ctx->embed, ctx->wpe, L0.x_in, T, d, ctx->V, ctx->npos));
   else CTX_RC(embed_fwd<AT>(st, ctx->d_ids, ctx->embed, L0.x_in, T, d, ctx->V));
   for (int l = 0; l < ctx->L; ++l) {
     LayerT<AT>& W = ctx->layers[l];
@@ -1240,6 +1252,14 @@ int tail_bwd(CtxT<AT>* ctx, LayerT<AT>& W, const Rows& rows, const TailBufsT<AT>
   return linear_bwd<AT>(ctx, B.dH, B.attn, W.proj[P_O], B.us_o, B.dattn, rows, gof(W.proj[P_O].W), 2);
 }
 
+// the seed of an attribution's backward pass, and the row statistics its log s(x) is read from: attr_seed over the labelled rows of the current batch
+template <typename AT>
+int attr_seed_rows(CtxT<AT>* ctx) {
+  const int* kinds = (const int*)ctx->attr_dev + ctx->Rmax;
+  return attr_seed<AT>(ctx->stream, ctx->logits, ctx->Vp, ctx->d_targets, ctx->attr_dev, kinds, kinds + ctx->Rmax, ctx->attr_nopt, ctx->cur_R, ctx->V, ctx->Vp, ctx->stats,
+                       ctx->dlogits, ctx->Vp);
+}
+
 // num_items: what the loss is normalised by (one slot); slot_items: per-slot counts of a stacked context (nullptr: every slot by its own labelled rows in this
 // batch). reduce_regions: a data-parallel full fine-tune's step -- the gradient regions are all-reduced on the communication stream as backward finishes them
 template <typename AT>
@@ -1275,9 +1295,7 @@ int backward(CtxT<AT>* ctx, int num_items, const int32_t* slot_items = nullptr, 
     CTX_HIP(hipMemsetAsync(ctx->tg + ctx->n_decay, 0, (size_t)(ctx->n_train - ctx->n_decay) * sizeof(float), st));
   }
   if (attr) {
-    const int* kinds = (const int*)ctx->attr_dev + ctx->Rmax;
-    CTX_RC(attr_seed<AT>(st, ctx->logits, ctx->Vp, ctx->d_targets, ctx->attr_dev, kinds, kinds + ctx->Rmax, ctx->attr_nopt, R, ctx->V, ctx->Vp, ctx->stats, ctx->dlogits,
-                         ctx->Vp));
+    CTX_RC(attr_seed_rows(ctx));
   } else if (ctx->ns == 1) {
     CTX_RC(logit_rows<AT>(st, ctx->logits, ctx->Vp, ctx->d_targets, R, ctx->V, ctx->stats, ctx->dlogits, ctx->Vp, inv_items, nullptr, 0, nullptr));
     CTX_RC(loss_reduce(st, ctx->stats, R, inv_items, ctx->d_loss));
@@ -2596,8 +2614,61 @@ int attr_reserve(tst_ctx* ctx) {
   return TST_OK;
 }
 
+// integrated gradients add the device baseline ids and the per-token sum to those (layout at tst_ctx::ig_dev)
+int ig_reserve(tst_ctx* ctx) {
+  const int64_t words = 2 * (int64_t)ctx->Tmax;
+  if (!ctx->ig_dev) {   // (kept at once: a failure further down must not leave the block to be allocated, and counted, a second time)
+    ctx->ig_dev = (float*)ctx->pool.alloc(words * 4);
+    if (!ctx->ig_dev) return fail(ctx, TST_ENOMEM, "hipMalloc failed: integrated-gradients buffers");
+    CTX_HIP(hipStreamSynchronize(nullptr));   // (the pool's zero fill, as in attr_reserve)
+  }
+  if (!ctx->h_ig) CTX_HIP(hipHostMalloc((void**)&ctx->h_ig, (size_t)(words + 8 * (int64_t)ctx->Rmax) * 4, hipHostMallocDefault));
+  return TST_OK;
+}
+
+// The passes of an integrated-gradients call, behind the uploads of attribute_async_impl (which clears ig_on / attr_pass whatever this returns). Everything is
+// enqueued at once -- a forward + head pass at the baseline (alpha = 0) and one at the real prompt (alpha = 1) for the two log s, then n_steps times
+// embed_interp(alpha_k) -> forward -> head -> backward -> token_ig -- with no host wait in between; the caller records one event behind the result copies.
 template <typename AT>
-int attribute_async_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* seq_kind, const int32_t* option_ids, int32_t n_opt) {
+int ig_enqueue(CtxT<AT>* ctx, const int32_t* baseline_ids, int n_steps) {
+  hipStream_t st = ctx->stream;
+  const int R = ctx->cur_R, S = ctx->cur_S, T = ctx->cur_T, Rmax = ctx->Rmax, Tmax = ctx->Tmax;
+  // the baseline ids follow the input ids onto the device: the tokens upload_batch kept, in its order
+  if (tsthost::trim_tokens_i32(baseline_ids, ctx->attr_cu_dev.data(), ctx->attr_cu_src.data(), S, (int32_t*)ctx->h_ig) != TST_OK)
+    return fail(ctx, TST_EINVAL, "internal: trim map");
+  int* d_bids = (int*)ctx->ig_dev;
+  float* d_acc = ctx->ig_dev + Tmax;
+  CTX_HIP(hipMemcpyAsync(d_bids, ctx->h_ig, (size_t)T * 4, hipMemcpyHostToDevice, st));
+  float* h_res = ctx->h_ig + Tmax;
+  ctx->ig_on = true;
+  for (int end = 0; end < 2; ++end) {   // log s at the baseline, then at the real prompt: attr_seed for the row statistics it leaves, no backward
+    ctx->ig_alpha = (float)end;
+    CTX_RC(forward(ctx, true));
+    CTX_RC(head_forward(ctx, true));
+    CTX_RC(attr_seed_rows(ctx));
+    CTX_HIP(hipMemcpyAsync(h_res + Tmax + (size_t)end * 4 * Rmax, ctx->stats, (size_t)R * 16, hipMemcpyDeviceToHost, st));
+  }
+  const float w = 1.0f / (float)n_steps;
+  for (int k = 1; k <= n_steps; ++k) {
+    ctx->ig_alpha = tsthost::ig_alpha(k, n_steps);
+    CTX_RC(forward(ctx, true));
+    CTX_RC(head_forward(ctx, true));
+    ctx->attr_pass = true;
+    const int brc = backward(ctx, R);
+    ctx->attr_pass = false;
+    CTX_RC(brc);
+    // (backward has joined its side streams: dX is the gradient at x_k; the step's term is taken against e - b from the table, not against x_k)
+    CTX_RC(token_ig<AT>(st, ctx->dX, ctx->embed, ctx->d_ids, d_bids, T, ctx->d, ctx->V, w, k == 1, d_acc));
+  }
+  ctx->ig_on = false;
+  CTX_HIP(hipMemcpyAsync(h_res, d_acc, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+  return TST_OK;
+}
+
+// ig = false: the plain attribution (one forward + head + backward, token_attr). ig = true: integrated gradients from baseline_ids over n_steps midpoints.
+template <typename AT>
+int attribute_async_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* seq_kind, const int32_t* option_ids, int32_t n_opt, const int32_t* baseline_ids = nullptr,
+                         int32_t n_steps = 0, bool ig = false) {
   if (!b) return TST_EINVAL;
   if (!ctx->finalized) return fail(ctx, TST_ESTATE, "weights not finalised");
   if (ctx->acc_active) return fail(ctx, TST_ESTATE, "an accumulation window is open on this context: an attribution would overwrite the micro-batch gradient path");
@@ -2607,11 +2678,13 @@ int attribute_async_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* seq_k
   {
     std::string perr;
     if (tsthost::plan_attribute(b, batch_limits(ctx), seq_kind, option_ids, n_opt, plan, perr) != TST_OK) return fail(ctx, TST_EINVAL, perr);
+    if (ig && tsthost::plan_ig(b, batch_limits(ctx), baseline_ids, n_steps, perr) != TST_OK) return fail(ctx, TST_EINVAL, perr);
   }
   CTX_RC(upload_batch(ctx, b, true, nullptr, 0));   // (the batch's own checks: nothing is copied or allocated for a refused batch)
   if (ctx->cur_R != plan.R) return fail(ctx, TST_EINVAL, "internal: labelled rows of plan_batch and plan_attribute differ");
   ctx->attr_S = -1;
   CTX_RC(attr_reserve(ctx));
+  if (ig) CTX_RC(ig_reserve(ctx));
   CTX_RC(ctx_event_sync(ctx, ctx->attr_evt));   // the staging image may still feed the previous attribution's copies
   hipStream_t st = ctx->stream;
   const int R = plan.R, S = ctx->cur_S, T = ctx->cur_T, Rmax = ctx->Rmax, Tmax = ctx->Tmax;
@@ -2628,6 +2701,17 @@ int attribute_async_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* seq_k
   ctx->attr_cu_dev.assign(h_cu, h_cu + S + 1);
   ctx->attr_cu_src.assign(b->cu_seqlens, b->cu_seqlens + S + 1);
   ctx->grad_stale = true;
+  if (ig) {
+    ctx->attr_plan = std::move(plan);
+    const int rc = ig_enqueue(ctx, baseline_ids, n_steps);
+    ctx->ig_on = false;
+    ctx->attr_pass = false;
+    CTX_RC(rc);
+    CTX_HIP(hipEventRecord(ctx->attr_evt, st));
+    ctx->attr_ig = true;
+    ctx->attr_S = S;
+    return TST_OK;
+  }
   CTX_RC(forward(ctx, true));
   CTX_RC(head_forward(ctx, true));
   ctx->attr_pass = true;
@@ -2643,6 +2727,7 @@ int attribute_async_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* seq_k
   CTX_HIP(hipMemcpyAsync(h_res + 2 * (size_t)Tmax, ctx->stats, (size_t)R * 16, hipMemcpyDeviceToHost, st));
   CTX_HIP(hipEventRecord(ctx->attr_evt, st));
   ctx->attr_plan = std::move(plan);
+  ctx->attr_ig = false;
   ctx->attr_S = S;
   return TST_OK;
 }
@@ -2819,6 +2904,7 @@ int tst_destroy(tst_ctx* ctx) {
   if (ctx->h_score) (void)hipHostFree(ctx->h_score);
   if (ctx->h_gen) (void)hipHostFree(ctx->h_gen);
   if (ctx->h_attr) (void)hipHostFree(ctx->h_attr);
+  if (ctx->h_ig) (void)hipHostFree(ctx->h_ig);
   if (ctx->attr_evt) (void)hipEventDestroy(ctx->attr_evt);
   if (ctx->gen_evt) (void)hipEventDestroy(ctx->gen_evt);
   if (ctx->score_evt) (void)hipEventDestroy(ctx->score_evt);
@@ -3191,6 +3277,7 @@ int tst_attribute_async(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_kin
 int tst_attribute_fetch(tst_ctx* ctx, float* gxi_out, float* gnorm_out, float* logs_out) {
   if (!ctx) return TST_EINVAL;
   if (ctx->attr_S < 0) return fail(ctx, TST_ESTATE, "tst_attribute_fetch without a pending tst_attribute_async");
+  if (ctx->attr_ig) return fail(ctx, TST_ESTATE, "the pending attribution is a tst_attribute_ig_async: fetch it with tst_attribute_ig_fetch");
   CTX_RC(ctx_event_sync(ctx, ctx->attr_evt));   // work enqueued after the attribution keeps running
   const int S = ctx->attr_S;
   ctx->attr_S = -1;
@@ -3208,6 +3295,35 @@ int tst_attribute(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_kind, con
   int rc = tst_attribute_async(ctx, b, seq_kind, option_ids, n_opt);
   if (rc != TST_OK) return rc;
   return tst_attribute_fetch(ctx, gxi_out, gnorm_out, logs_out);
+}
+
+int tst_attribute_ig_async(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_kind, const int32_t* option_ids, int32_t n_opt, const int32_t* baseline_ids,
+                           int32_t n_steps) {
+  if (!ctx || !b) return TST_EINVAL;
+  return typed(ctx, [&](auto* c) { return attribute_async_impl(c, b, seq_kind, option_ids, n_opt, baseline_ids, n_steps, true); });
+}
+
+int tst_attribute_ig_fetch(tst_ctx* ctx, float* ig_out, float* logs_out, float* logs_base_out) {
+  if (!ctx) return TST_EINVAL;
+  if (ctx->attr_S < 0) return fail(ctx, TST_ESTATE, "tst_attribute_ig_fetch without a pending tst_attribute_ig_async");
+  if (!ctx->attr_ig) return fail(ctx, TST_ESTATE, "the pending attribution is a tst_attribute_async: fetch it with tst_attribute_fetch");
+  CTX_RC(ctx_event_sync(ctx, ctx->attr_evt));   // work enqueued after the attribution keeps running
+  const int S = ctx->attr_S;
+  ctx->attr_S = -1;
+  ctx->attr_ig = false;
+  const float* h_res = ctx->h_ig + ctx->Tmax;
+  if (ig_out && tsthost::untrim_tokens(h_res, ctx->attr_cu_dev.data(), ctx->attr_cu_src.data(), S, ig_out) != TST_OK) return fail(ctx, TST_EINVAL, "internal: un-trim map");
+  const float* h_stats = h_res + ctx->Tmax;
+  if (logs_base_out) tsthost::attr_logs(h_stats, ctx->attr_plan, S, logs_base_out);
+  if (logs_out) tsthost::attr_logs(h_stats + 4 * (size_t)ctx->Rmax, ctx->attr_plan, S, logs_out);
+  return TST_OK;
+}
+
+int tst_attribute_ig(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_kind, const int32_t* option_ids, int32_t n_opt, const int32_t* baseline_ids, int32_t n_steps,
+                     float* ig_out, float* logs_out, float* logs_base_out) {
+  int rc = tst_attribute_ig_async(ctx, b, seq_kind, option_ids, n_opt, baseline_ids, n_steps);
+  if (rc != TST_OK) return rc;
+  return tst_attribute_ig_fetch(ctx, ig_out, logs_out, logs_base_out);
 }
 
 int tst_generate_async(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, const int32_t* eos_ids, int32_t n_eos) {

@@ -112,4 +112,21 @@ int tst_host_untrim_tokens(const float* src, const int32_t* cu_dev, const int32_
   return tsthost::untrim_tokens(src, cu_dev, cu_src, n_seqs, dst);
 }
 
+int tst_host_plan_ig(const tst_model_cfg* cfg, const tst_batch* b, const int32_t* baseline_ids, int n_steps, float* alpha_out, char* err_out, int err_cap) {
+  if (!cfg) return TST_EINVAL;
+  std::string err;
+  const int rc = tsthost::plan_ig(b, limits_of(*cfg), baseline_ids, n_steps, err);
+  if (err_out && err_cap > 0) {
+    strncpy(err_out, err.c_str(), (size_t)err_cap - 1);
+    err_out[err_cap - 1] = 0;
+  }
+  if (rc != TST_OK) return rc;
+  for (int k = 1; alpha_out && k <= n_steps; ++k) alpha_out[k - 1] = tsthost::ig_alpha(k, n_steps);
+  return TST_OK;
+}
+
+int tst_host_trim_tokens(const int32_t* src, const int32_t* cu_dev, const int32_t* cu_src, int n_seqs, int32_t* dst) {
+  return tsthost::trim_tokens_i32(src, cu_dev, cu_src, n_seqs, dst);
+}
+
 }  // extern "C"

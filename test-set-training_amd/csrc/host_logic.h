@@ -375,4 +375,36 @@ inline int untrim_tokens(const float* src, const int32_t* cu_dev, const int32_t*
   return TST_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ integrated gradients: what they add to an attribution
+// tst_attribute_ig_async walks the embedding-layer output from b[t] = embed_tokens[baseline_ids[t]] to the real e[t] in n_steps midpoint steps. plan_ig refuses,
+// BEFORE anything is allocated or launched, what plan_attribute and plan_batch do not look at: the baseline ids (host memory, one per token of the caller's batch,
+// inside the vocabulary) and the step count. The batch is only read for n_tokens, which plan_attribute has checked by then.
+constexpr int kIgMaxSteps = 256;   // == TST_IG_MAX_STEPS
+inline int plan_ig(const tst_batch* b, const BatchLimits& lim, const int32_t* baseline_ids, int n_steps, std::string& err) {
+  auto fail = [&](const char* m) { err = m; return TST_EINVAL; };
+  if (!b) return fail("null batch");
+  if (n_steps < 1 || n_steps > kIgMaxSteps) return fail("n_steps out of range (1..256)");
+  if (!baseline_ids) return fail("null baseline_ids");
+  if (b->n_tokens <= 0 || b->n_tokens > lim.Tmax) return fail("batch exceeds max_tokens/max_seqs or is empty");
+  for (int t = 0; t < b->n_tokens; ++t)
+    if (baseline_ids[t] < 0 || baseline_ids[t] >= lim.V) return fail("baseline id out of vocabulary");
+  return TST_OK;
+}
+// alpha of midpoint step k = 1 .. m, in fp32 as the engine passes it to embed_interp
+inline float ig_alpha(int k, int m) { return ((float)k - 0.5f) / (float)m; }
+// The inverse of untrim_tokens for per-token inputs: the caller's tokens (sequence s at [cu_src[s], cu_src[s + 1])) into the order the device runs them
+// (sequence s at [cu_dev[s], cu_dev[s + 1]), its first tokens; trim_last_token drops the last one). The baseline ids follow the input ids through it.
+inline int trim_tokens_i32(const int32_t* src, const int32_t* cu_dev, const int32_t* cu_src, int S, int32_t* dst) {
+  if (!src || !cu_dev || !cu_src || !dst || S < 0) return TST_EINVAL;
+  for (int s = 0; s < S; ++s) {
+    const int nd = cu_dev[s + 1] - cu_dev[s], ns = cu_src[s + 1] - cu_src[s];
+    if (cu_dev[s] < 0 || cu_src[s] < 0 || nd < 0 || ns < nd) return TST_EINVAL;
+  }
+  for (int s = 0; s < S; ++s) {
+    const int nd = cu_dev[s + 1] - cu_dev[s];
+    for (int p = 0; p < nd; ++p) dst[cu_dev[s] + p] = src[cu_src[s] + p];
+  }
+  return TST_OK;
+}
+
 }  // namespace tsthost

@@ -339,9 +339,52 @@ static void test_attribute() {
   CHECK(untrim_tokens(nullptr, cu1, cu1, 1, one) == TST_EINVAL);
 }
 
+// integrated gradients: plan_ig's refusals, the midpoints, and the baseline ids' way onto the device
+static void test_ig() {
+  const int32_t cu[4] = {0, 1, 3, 8};
+  const int32_t ids[8] = {1, 2, 3, 4, 5, 6, 7, 8};
+  tst_batch b;
+  memset(&b, 0, sizeof(b));
+  b.input_ids = ids; b.cu_seqlens = cu; b.n_seqs = 3; b.n_tokens = 8;
+  const BatchLimits lim = {16, 4, 8, 50, 16, 1};
+  const int32_t base[8] = {1, 1, 1, 1, 1, 49, 0, 8};
+  std::string err;
+  CHECK(plan_ig(&b, lim, base, 1, err) == TST_OK);
+  CHECK(plan_ig(&b, lim, base, kIgMaxSteps, err) == TST_OK);
+  CHECK(plan_ig(&b, lim, base, 0, err) == TST_EINVAL && err.find("n_steps") != std::string::npos);
+  CHECK(plan_ig(&b, lim, base, kIgMaxSteps + 1, err) == TST_EINVAL && err.find("n_steps") != std::string::npos);
+  CHECK(plan_ig(&b, lim, nullptr, 4, err) == TST_EINVAL && err.find("null baseline_ids") != std::string::npos);
+  CHECK(plan_ig(nullptr, lim, base, 4, err) == TST_EINVAL);
+  { int32_t bad[8]; memcpy(bad, base, sizeof(bad)); bad[7] = 50; CHECK(plan_ig(&b, lim, bad, 4, err) == TST_EINVAL && err.find("baseline id") != std::string::npos);
+    bad[7] = 8; bad[0] = -1; CHECK(plan_ig(&b, lim, bad, 4, err) == TST_EINVAL && err.find("baseline id") != std::string::npos); }
+  { tst_batch e = b; e.n_tokens = 17; CHECK(plan_ig(&e, lim, base, 4, err) == TST_EINVAL); e.n_tokens = 0; CHECK(plan_ig(&e, lim, base, 4, err) == TST_EINVAL); }
+  // (the baseline ids are read up to n_tokens and no further: an exactly sized heap array under the sanitizer)
+  { std::unique_ptr<int32_t[]> hb(new int32_t[8]); memcpy(hb.get(), base, sizeof(base)); CHECK(plan_ig(&b, lim, hb.get(), 16, err) == TST_OK); }
+  CHECK(ig_alpha(1, 1) == 0.5f && ig_alpha(1, 16) == 0.03125f && ig_alpha(16, 16) == 0.96875f && ig_alpha(8, 16) == 0.46875f);
+  for (int m = 1; m <= kIgMaxSteps; ++m) CHECK(ig_alpha(1, m) > 0.0f && ig_alpha(m, m) < 1.0f);
+  // trim: lengths 1 (never trimmed), 2 and 5
+  const int32_t cu_trim[4] = {0, 1, 2, 6};
+  std::unique_ptr<int32_t[]> dst(new int32_t[6]);
+  CHECK(trim_tokens_i32(base, cu_trim, cu, 3, dst.get()) == TST_OK);
+  const int32_t want[6] = {1, 1, 1, 1, 49, 0};
+  for (int t = 0; t < 6; ++t) CHECK(dst[(size_t)t] == want[t]);
+  std::unique_ptr<int32_t[]> dst8(new int32_t[8]);
+  CHECK(trim_tokens_i32(base, cu, cu, 3, dst8.get()) == TST_OK);
+  for (int t = 0; t < 8; ++t) CHECK(dst8[(size_t)t] == base[t]);
+  // trim, then un-trim of a per-token result: the round trip of a token's value, 0 where the device did not run it
+  { float f[6], back[8]; for (int t = 0; t < 6; ++t) f[t] = (float)dst[(size_t)t];
+    CHECK(untrim_tokens(f, cu_trim, cu, 3, back) == TST_OK);
+    for (int t = 0; t < 8; ++t) CHECK(back[t] == ((t == 2 || t == 7) ? 0.0f : (float)base[t])); }
+  const int32_t cu1[2] = {0, 1}, cu2[2] = {0, 2};
+  CHECK(trim_tokens_i32(base, cu2, cu1, 1, dst.get()) == TST_EINVAL);   // longer on the device than in the caller's batch
+  CHECK(trim_tokens_i32(nullptr, cu1, cu1, 1, dst.get()) == TST_EINVAL);
+  CHECK(trim_tokens_i32(base, cu1, cu1, 0, dst.get()) == TST_OK);
+}
+
 int main() {
   test_plan_generate();
   test_attribute();
+  test_ig();
   test_plan_batch();
   test_zero_and_layout();
   if (g_fail) { fprintf(stderr, "%d checks failed\n", g_fail); return 1; }

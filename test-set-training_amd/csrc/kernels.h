@@ -156,6 +156,12 @@ template <typename AT> int attr_seed(hipStream_t st, const float* logits, long l
                                      int n_opt, int n_rows, int V, int Vp, float* stats, AT* dlogits, long ldd);
 // token_attr: gxi[t] = sum_c g[t, c] e[t, c], gnorm[t] = sqrt(sum_c g[t, c]^2) for T rows of d columns (a multiple of 8, at most 8192); one wave per token, fp32
 template <typename AT> int token_attr(hipStream_t st, const AT* g, const AT* e, int T, int d, float* gxi, float* gnorm);
+// integrated gradients (tst_attribute_ig_async). embed_interp: out[t, :] = E[bids[t]] + alpha (E[ids[t]] - E[bids[t]]) (+ P[pos[t]] when P != nullptr: GPT-2) in fp32,
+// ONE rounding; alpha == 1 writes what embed_fwd / embed_pos_fwd write, bit for bit, and a token with bids[t] == ids[t] gets its table row at every alpha.
+// token_ig: acc[t] = (first ? 0 : acc[t]) + w sum_c g[t, c] (E[ids[t], c] - E[bids[t], c]). One wave per token; d a multiple of 8; ids clamped into [0, vocab).
+template <typename AT> int embed_interp(hipStream_t st, const int* ids, const int* bids, const int* pos, const AT* E, const AT* P, AT* out, int T, int d, int vocab,
+                                        int npos, float alpha);
+template <typename AT> int token_ig(hipStream_t st, const AT* g, const AT* E, const int* ids, const int* bids, int T, int d, int vocab, float w, bool first, float* acc);
 int ids_gather(hipStream_t st, const int* src, int* ids, int n, int n_src);    // ids[i] = src[ids[i]] (device-side batch of a trimmed TST_BATCH_DEVICE_IDS call)
 int ids_check(hipStream_t st, const int* ids, int T, int vocab, int* flag);   // *flag = 1 when an id lies outside [0, vocab)
 template <typename AT> int cast_from_f32(hipStream_t st, const float* in, AT* out, long n, float scale);

@@ -250,6 +250,20 @@ int tst_k_token_attr(const void* g, const void* e, int T, int d, float* gxi, flo
   return token_attr<bf16_t>(nullptr, (const bf16_t*)g, (const bf16_t*)e, T, d, gxi, gnorm);
 }
 int tst_k_token_attr_f32(const float* g, const float* e, int T, int d, float* gxi, float* gnorm) { return token_attr<float>(nullptr, g, e, T, d, gxi, gnorm); }
+int tst_k_embed_interp(const int32_t* ids, const int32_t* bids, const int32_t* pos, const void* E, const void* P, void* out, int T, int d, int vocab, int npos,
+                       float alpha) {
+  return embed_interp<bf16_t>(nullptr, ids, bids, pos, (const bf16_t*)E, (const bf16_t*)P, (bf16_t*)out, T, d, vocab, npos, alpha);
+}
+int tst_k_embed_interp_f32(const int32_t* ids, const int32_t* bids, const int32_t* pos, const float* E, const float* P, float* out, int T, int d, int vocab, int npos,
+                           float alpha) {
+  return embed_interp<float>(nullptr, ids, bids, pos, E, P, out, T, d, vocab, npos, alpha);
+}
+int tst_k_token_ig(const void* g, const void* E, const int32_t* ids, const int32_t* bids, int T, int d, int vocab, float w, int first, float* acc) {
+  return token_ig<bf16_t>(nullptr, (const bf16_t*)g, (const bf16_t*)E, ids, bids, T, d, vocab, w, first != 0, acc);
+}
+int tst_k_token_ig_f32(const float* g, const float* E, const int32_t* ids, const int32_t* bids, int T, int d, int vocab, float w, int first, float* acc) {
+  return token_ig<float>(nullptr, g, E, ids, bids, T, d, vocab, w, first != 0, acc);
+}
 int tst_k_attn_fwd(const void* qkv, int64_t ld, const int32_t* cu, int n_seqs, int max_len, void* out, int64_t ldo, float* lse, int T, int H, int Hkv, int dh,
                    float scale) {
   return attn_fwd(nullptr, (const bf16_t*)qkv, ld, cu, n_seqs, max_len, (bf16_t*)out, ldo, lse, T, H, Hkv, dh, scale);

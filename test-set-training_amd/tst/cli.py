@@ -95,6 +95,13 @@ def build_parser():
                        "per held-out batch; include/tst_hip.h tst_attribute_async): the records gain attr = {gxi, gnorm} over the prompt tokens and, with a "
                        "tokenizer, attr_top. Off: the run is unchanged. Not with --dp > 1 or --layout dp-stacked")
         p.add_argument("--attribute-top", type=int, default=5, help="with --attribute: tokens listed in attr_top (largest gradient norm first)")
+        p.add_argument("--attribute-ig", type=int, default=0, metavar="STEPS", help="also attribute every held-out sample's score to its prompt tokens by "
+                       "integrated gradients over STEPS midpoint steps (1..256; about STEPS forward + backward passes plus two forward passes per held-out batch; include/tst_hip.h "
+                       "tst_attribute_ig_async): the prompt tokens are walked from --attribute-baseline-id to their own embeddings, the answer tokens stay; the "
+                       "records gain attr_ig = {ig, log_s_base, delta} and, with a tokenizer, attr_ig_top (--attribute-top tokens, largest |ig| first, signed). "
+                       "0: off, the run is unchanged. Not with --dp > 1 or --layout dp-stacked")
+        p.add_argument("--attribute-baseline-id", type=int, default=None, metavar="ID", help="with --attribute-ig: the token id of the baseline prompt; default: "
+                       "the tokenizer's pad id, else the checkpoint's pad_token_id, else its first eos id, else 0 (the choice is recorded in the train log)")
         if name == "prune":
             p.add_argument("--rounds", type=int, default=4)
             p.add_argument("--tau", type=float, default=0.5)
@@ -160,6 +167,31 @@ def parse_eos_ids(a):
     return tuple(int(x) for x in (e if isinstance(e, (list, tuple)) else [e]))
 
 
+def default_baseline_id(a):
+    """(id, where it came from) of the integrated-gradients baseline prompt when --attribute-baseline-id is not given: the tokenizer's pad id, else pad_token_id
+    of the checkpoint's config, else its first eos id, else 0"""
+    tok_file = getattr(a, "tokenizer", None) or (os.path.join(a.model_dir, "tokenizer.json") if getattr(a, "model_dir", None) else None)
+    if tok_file and os.path.exists(tok_file):
+        try:
+            from tokenizers import Tokenizer
+            pad = Tokenizer.from_file(tok_file).padding
+            if pad and pad.get("pad_id") is not None:
+                return int(pad["pad_id"]), "tokenizer pad id"
+        except ImportError:
+            pass
+    for name in ("generation_config.json", "config.json"):
+        path = os.path.join(a.model_dir, name) if getattr(a, "model_dir", None) else None
+        if path and os.path.exists(path):
+            with open(path) as fh:
+                p = json.load(fh).get("pad_token_id")
+            if p is not None:
+                return int(p), f"pad_token_id of {name}"
+    eos = default_eos_ids(getattr(a, "model_dir", None))
+    if eos:
+        return int(eos[0]), "eos id"
+    return 0, "default"
+
+
 def _args_to_train(a):
     from .trainer import TrainArgs
     gen = dict(generate=True, max_new_tokens=int(a.max_new_tokens), eos_ids=parse_eos_ids(a)) if getattr(a, "generate", False) else {}
@@ -169,6 +201,20 @@ def _args_to_train(a):
         if int(a.attribute_top) < 0:
             raise SystemExit("--attribute-top must be >= 0")
         gen.update(attribute=True, attribute_top=int(a.attribute_top))
+    if int(getattr(a, "attribute_ig", 0) or 0) != 0:
+        if getattr(a, "dp", 1) > 1 or getattr(a, "layout", None) == "dp-stacked":
+            raise SystemExit("--attribute-ig is not available on the data-parallel layouts (--dp > 1, --layout dp-stacked)")
+        if not 1 <= int(a.attribute_ig) <= 256:
+            raise SystemExit("--attribute-ig must be 1..256 steps (0: off)")
+        if int(a.attribute_top) < 0:
+            raise SystemExit("--attribute-top must be >= 0")
+        bid = getattr(a, "attribute_baseline_id", None)
+        bid, a.attribute_baseline_source = (int(bid), "--attribute-baseline-id") if bid is not None else default_baseline_id(a)
+        if bid < 0:
+            raise SystemExit("--attribute-baseline-id must be a token id (>= 0)")
+        gen.update(attribute_ig=int(a.attribute_ig), attribute_baseline_id=bid, attribute_top=int(a.attribute_top))
+    elif getattr(a, "attribute_baseline_id", None) is not None:
+        raise SystemExit("--attribute-baseline-id needs --attribute-ig STEPS")
     return TrainArgs(**gen, learning_rate=a.learning_rate, num_train_epochs=a.num_train_epochs, per_device_train_batch_size=a.per_device_train_batch_size,
                      warmup_steps=a.warmup_steps, weight_decay=a.weight_decay, max_grad_norm=a.max_grad_norm, seed=a.seed, lora_r=a.lora_r,
                      lora_alpha=a.lora_alpha, logging_steps=a.logging_steps, gradient_accumulation_steps=max(1, a.gradient_accumulation_steps))
@@ -274,7 +320,7 @@ def main(argv=None):
         samples, opt_ids = TIO.load_qa_jsonl(a.data_file, tok, max_len=a.max_len)
         targs.option_ids = tuple(opt_ids)
     decode = None
-    if targs.generate:
+    if targs.generate or targs.attribute_ig > 0:
         tok_file = a.tokenizer or (os.path.join(a.model_dir, "tokenizer.json") if a.model_dir else None)
         if tok_file and os.path.exists(tok_file):
             from tokenizers import Tokenizer
@@ -282,6 +328,8 @@ def main(argv=None):
             decode = lambda ids: _tk.decode(list(ids))   # noqa: E731
     max_answer = max((len(x.ids) - x.n_prompt for x in samples), default=4) if samples else 4
     ctx, cfg = _make_ctx(a, targs, local_rank, rank, world, max_answer)   # a list: the root context and its resident forks
+    if targs.attribute_ig > 0 and targs.attribute_baseline_id >= cfg["vocab_size"]:
+        raise SystemExit(f"--attribute-baseline-id {targs.attribute_baseline_id} lies outside the model's vocabulary ({cfg['vocab_size']})")
     if samples is None:
         samples = D.synth_vsi(a.n_samples, cfg["vocab_size"])
     by_id = {s.sid: s for s in samples}
@@ -295,6 +343,8 @@ def main(argv=None):
         log_fh.write(json.dumps(rec) + "\n")
         log_fh.flush()
 
+    if targs.attribute_ig > 0:   # the run's metadata: which baseline prompt the attr_ig of its records was walked from
+        log(dict(event="attribute_ig", steps=targs.attribute_ig, baseline_id=targs.attribute_baseline_id, baseline_from=a.attribute_baseline_source))
     if a.layout == "dp-stacked":
         if a.train_mode != "lora" or a.dp > 1:
             raise SystemExit("--layout dp-stacked is the LoRA layout and excludes --dp")

@@ -10,6 +10,10 @@ eos token), "gen_correct" (it starts with the reference answer's ids) and, when 
 With TrainArgs.attribute every record also carries which prompt tokens its score rests on: "attr" = {"gxi": [...], "gnorm": [...]} over the prompt tokens
 (gradient x input and gradient norm of log s(x) per token, include/tst_hip.h tst_attribute_async) and, with a `decode` function, "attr_top": the
 TrainArgs.attribute_top tokens of largest gnorm, as text. Not available on the data-parallel layouts.
+With TrainArgs.attribute_ig > 0 every record also carries "attr_ig" = {"ig": [...], "log_s_base": float, "delta": float}: the integrated gradients of log s(x) over
+the prompt tokens, walked from a prompt of TrainArgs.attribute_baseline_id tokens in attribute_ig steps (include/tst_hip.h tst_attribute_ig_async), log s of that
+baseline prompt, and the completeness gap sum(ig) - (log s - log s_base); with a `decode` function also "attr_ig_top": the attribute_top tokens of largest |ig| as
+[text, ig] pairs, signed. Not available on the data-parallel layouts either.
 """
 import json
 import os
@@ -20,11 +24,13 @@ import numpy as np
 
 from . import kfold
 from .trainer import (attribute_heldout, attribute_heldout_concurrent, attribute_heldout_stacked)
+from .trainer import (attribute_ig_heldout, attribute_ig_heldout_concurrent, attribute_ig_heldout_stacked)
 from .trainer import (TrainArgs, fine_tune, fine_tune_concurrent, fine_tune_dp, fine_tune_stacked, generate_heldout, generate_heldout_concurrent,
                       generate_heldout_stacked, score_heldout, score_heldout_concurrent, score_heldout_stacked)
 
 GEN_ARGS = ("generate", "max_new_tokens", "eos_ids")   # TrainArgs fields that enter the run fingerprint only when generation is on
 ATTR_ARGS = ("attribute", "attribute_top")             # TrainArgs settings that enter it only when attribution is on
+IG_ARGS = ("attribute_ig", "attribute_baseline_id")    # likewise, when integrated gradients are on (attribute_top then enters too: it sizes attr_ig_top)
 
 
 def run_fingerprint(samples, k, args, extra=None):
@@ -42,6 +48,11 @@ def run_fingerprint(samples, k, args, extra=None):
         a.update({kk: getattr(args, kk) for kk in ATTR_ARGS})
     elif not a.get("attribute"):
         for kk in ATTR_ARGS:
+            a.pop(kk, None)
+    if int(getattr(args, "attribute_ig", 0) or 0) > 0:
+        a.update({kk: getattr(args, kk) for kk in IG_ARGS + ("attribute_top",)})
+    else:
+        for kk in IG_ARGS:
             a.pop(kk, None)
     h.update(json.dumps(dict(args={kk: (list(v) if isinstance(v, tuple) else v) for kk, v in sorted(a.items())}, k=int(k), n=len(samples),
                              extra=extra or {}), sort_keys=True).encode())
@@ -90,9 +101,9 @@ def train_health(recs):
                 grad_norm_min=float(gn.min()), grad_norm_max=float(gn.max()))
 
 
-def fold_records(held, f, rnd, s, pred, correct, gen=None, decode=None, attr=None, attr_top=5):
+def fold_records(held, f, rnd, s, pred, correct, gen=None, decode=None, attr=None, attr_top=5, ig=None):
     """the records of one scored held-out fold; gen = [(gen ids, gen_correct)] per sample when generation is on, decode = ids -> text;
-    attr = tst.score.token_attribution's dict per sample when attribution is on"""
+    attr = tst.score.token_attribution's dict per sample when attribution is on; ig = tst.score.token_ig's when integrated gradients are"""
     records = [dict(id=int(x.sid), fold=int(f), round=int(rnd), s=float(si), pred=int(pi), correct=int(ci), kind=x.kind)
                for x, si, pi, ci in zip(held, s, pred, correct)]
     if gen is not None:
@@ -107,6 +118,12 @@ def fold_records(held, f, rnd, s, pred, correct, gen=None, decode=None, attr=Non
             if decode is not None:
                 top = np.argsort(-np.asarray(a["gnorm"], np.float64), kind="stable")[:max(0, int(attr_top))]
                 r["attr_top"] = [decode([int(x.ids[t])]) for t in top]
+    if ig is not None:
+        for r, x, a in zip(records, held, ig):
+            r["attr_ig"] = dict(ig=[float(v) for v in a["ig"]], log_s_base=float(a["log_s_base"]), delta=float(a["delta"]))
+            if decode is not None:
+                top = np.argsort(-np.abs(np.asarray(a["ig"], np.float64)), kind="stable")[:max(0, int(attr_top))]
+                r["attr_ig_top"] = [[decode([int(x.ids[t])]), float(a["ig"][t])] for t in top]
     return records
 
 
@@ -125,8 +142,9 @@ def run_fold(ctx, samples, assign, f, args: TrainArgs, rnd=0, out_dir=None, log=
     s, pred, correct = score_heldout(ctx, held, args)
     gen = generate_heldout(ctx, held, args) if args.generate else None
     attr = attribute_heldout(ctx, held, args) if args.attribute else None
+    ig = attribute_ig_heldout(ctx, held, args) if args.attribute_ig > 0 else None
     t2 = time.perf_counter()
-    records = fold_records(held, f, rnd, s, pred, correct, gen, decode, attr, args.attribute_top)
+    records = fold_records(held, f, rnd, s, pred, correct, gen, decode, attr, args.attribute_top, ig)
     if out_dir:
         _write_shard(out_dir, rnd, f, records)
     stats = dict(fold=f, n_train=len(train_idx), n_heldout=len(held_idx), train_s=t1 - t0, score_s=t2 - t1,
@@ -160,13 +178,14 @@ def run_fold_group(ctxs, samples, assign, fold_ids, args: TrainArgs, rnd=0, out_
     scored = (score_heldout_stacked if stacked else score_heldout_concurrent)(ctxs, helds, args)
     gens = (generate_heldout_stacked if stacked else generate_heldout_concurrent)(ctxs, helds, args) if args.generate else [None] * len(helds)
     attrs = (attribute_heldout_stacked if stacked else attribute_heldout_concurrent)(ctxs, helds, args) if args.attribute else [None] * len(helds)
+    igs = (attribute_ig_heldout_stacked if stacked else attribute_ig_heldout_concurrent)(ctxs, helds, args) if args.attribute_ig > 0 else [None] * len(helds)
     t2 = time.perf_counter()
     if os.environ.get("TST_PHASE_LOG"):
         import sys
         print(f"[phase] fold group {list(fold_ids)}: train {t1 - t0:.3f} s, score {t2 - t1:.3f} s", file=sys.stderr)
     all_records, stats = [], []
-    for f, (tr, he), held, (s, pred, correct), gen, attr, lg in zip(fold_ids, idx, helds, scored, gens, attrs, logs):
-        records = fold_records(held, f, rnd, s, pred, correct, gen, decode, attr, args.attribute_top)
+    for f, (tr, he), held, (s, pred, correct), gen, attr, ig, lg in zip(fold_ids, idx, helds, scored, gens, attrs, igs, logs):
+        records = fold_records(held, f, rnd, s, pred, correct, gen, decode, attr, args.attribute_top, ig)
         if out_dir:
             _write_shard(out_dir, rnd, f, records)
         all_records += records
@@ -214,7 +233,7 @@ def diagnose_dp(ctx, samples, k, args: TrainArgs, rank, world, dp, rnd=0, out_di
     group scores the held-out fold and writes the shard. Returns (records, stats) of the folds this rank wrote (empty on the
     group's other ranks)."""
     from . import ddp
-    if args.attribute:
+    if args.attribute or args.attribute_ig > 0:
         raise ValueError("token attribution is not available on data-parallel contexts (include/tst_hip.h tst_attribute_async)")
     g, n_groups, dp_rank, _ = ddp.dp_layout(rank, world, dp)
     assign = kfold.kfold_assign(len(samples), k, True, args.seed)
@@ -255,7 +274,7 @@ def diagnose_dp_stacked(ctxs, samples, k, args: TrainArgs, rank, world, rnd=0, o
     r, r + world, ... of every held-out fold. Returns (records of this rank's part, per-fold stats). With out_dir the parts are brought
     together by `gather(obj) -> list over ranks on rank 0` (default: torch.distributed.gather_object) and rank 0 writes the fold shards."""
     group = list(ctxs) if isinstance(ctxs, (list, tuple)) else [ctxs]
-    if args.attribute:
+    if args.attribute or args.attribute_ig > 0:
         raise ValueError("token attribution is not available on data-parallel contexts (include/tst_hip.h tst_attribute_async)")
     cap = sum(getattr(c, "n_stack", 1) for c in group)
     assign = kfold.kfold_assign(len(samples), k, True, args.seed)

@@ -138,6 +138,9 @@ SIGNATURES = {
     "tst_attribute_async": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.c_int32]),
     "tst_attribute_fetch": (C.c_int, [_P, _P, _P, _P]),
     "tst_attribute": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.c_int32, _P, _P, _P]),
+    "tst_attribute_ig_async": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.c_int32, _P, C.c_int32]),
+    "tst_attribute_ig_fetch": (C.c_int, [_P, _P, _P, _P]),
+    "tst_attribute_ig": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     "tst_profile_enable": (C.c_int, [_P, _I]),
     "tst_profile_read": (C.c_int, [_P, _I, _I, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_L), _I]),
     "tst_profile_intervals": (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _L, C.POINTER(_L)]),
@@ -183,6 +186,10 @@ LAB_SIGNATURES = {
     "tst_k_attr_seed_f32": (C.c_int, [_P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _L]),
     "tst_k_token_attr": (C.c_int, [_P, _P, _I, _I, _P, _P]),
     "tst_k_token_attr_f32": (C.c_int, [_P, _P, _I, _I, _P, _P]),
+    "tst_k_embed_interp": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F]),
+    "tst_k_embed_interp_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F]),
+    "tst_k_token_ig": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
+    "tst_k_token_ig_f32": (C.c_int, [_P, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
     "tst_k_attn_fwd": (C.c_int, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _I, _F]),
     "tst_k_attn_bwd": (C.c_int, [_P, _L, _P, _L, _P, _L, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _F]),
     "tst_k_attn_fwd_rope": (C.c_int, [_P, _L, _P, _I, _I, _P, _L, _P, _I, _I, _I, _I, _F, _P, _P]),
@@ -221,6 +228,8 @@ HOST_SIGNATURES = {
     "tst_host_cut_at_eos": (C.c_int, [_P, _P, _P, _I, _I, _P, _I]),
     "tst_host_plan_attribute": (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I]),
     "tst_host_untrim_tokens": (C.c_int, [_P, _P, _P, _I, _P]),
+    "tst_host_plan_ig": (C.c_int, [_P, _P, _P, _I, _P, _P, _I]),
+    "tst_host_trim_tokens": (C.c_int, [_P, _P, _P, _I, _P]),
 }
 
 
@@ -392,6 +401,39 @@ def host_untrim_tokens(values, cu_dev, cu_src):
     if load_host().tst_host_untrim_tokens(_ptr(src), _ptr(cd), _ptr(cs), len(cd) - 1, _ptr(dst)) != 0:
         raise TstError("tst_host_untrim_tokens: bad arguments")
     return dst[:int(cs[-1])]
+
+
+IG_MAX_STEPS = 256   # TST_IG_MAX_STEPS
+
+
+def host_plan_ig(mc, ids, cu, baseline_ids, n_steps):
+    """tsthost::plan_ig through the CPU library: the n_steps midpoints alpha_k (fp32) of an integrated-gradients call; raises TstError with the library's
+    message for a refusal (baseline_ids None, an id outside the vocabulary, n_steps outside 1 .. IG_MAX_STEPS)"""
+    L = load_host()
+    ids = np.ascontiguousarray(ids, np.int32)
+    cu = np.ascontiguousarray(cu, np.int32)
+    base = None if baseline_ids is None else np.ascontiguousarray(baseline_ids, np.int32)
+    if base is not None and len(base) != len(ids):
+        raise TstError("baseline_ids needs one entry per token")
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    b = Batch(ip(ids), None, ip(cu), len(cu) - 1, len(ids), None, 0)
+    alpha, err = np.zeros(IG_MAX_STEPS, np.float32), C.create_string_buffer(256)
+    rc = L.tst_host_plan_ig(C.byref(mc), C.byref(b), None if base is None else _ptr(base), int(n_steps), _ptr(alpha), err, 256)
+    if rc != 0:
+        raise TstError(err.value.decode() or f"tst_host_plan_ig rc={rc}")
+    return alpha[:int(n_steps)].copy()
+
+
+def host_trim_tokens(values, cu_dev, cu_src):
+    """per-token ids of the caller's batch -> the order the device runs them (a trimmed token is dropped), as tst_attribute_ig_async uploads the baseline ids"""
+    src = np.ascontiguousarray(values, np.int32)
+    cd, cs = np.ascontiguousarray(cu_dev, np.int32), np.ascontiguousarray(cu_src, np.int32)
+    if len(cd) != len(cs) or len(cd) < 1 or len(src) < int(cs[-1]):
+        raise TstError("tst_host_trim_tokens: bad arguments")
+    dst = np.full(max(1, int(cd[-1])), -1, np.int32)
+    if load_host().tst_host_trim_tokens(_ptr(src), _ptr(cd), _ptr(cs), len(cd) - 1, _ptr(dst)) != 0:
+        raise TstError("tst_host_trim_tokens: bad arguments")
+    return dst[:int(cd[-1])]
 
 
 def device_count():
@@ -920,6 +962,36 @@ class Context:
     def attribute(self, ids, labels, cu, seq_kind=None, option_ids=(), seq_slot=None):
         self.attribute_async(ids, labels, cu, seq_kind, option_ids, seq_slot)
         return self.attribute_fetch()
+
+    # ---- integrated gradients (include/tst_hip.h tst_attribute_ig_async)
+    def attribute_ig_async(self, ids, labels, cu, baseline_ids, n_steps, seq_kind=None, option_ids=(), seq_slot=None):
+        """enqueue the integrated gradients of log s(x) from the baseline prompt baseline_ids (host ids, one per token; a token whose baseline is its own id is not
+        interpolated) to the packed batch, n_steps midpoint steps. seq_kind / option_ids as for attribute_async. Results come from attribute_ig_fetch()."""
+        b, keep = self._batch(ids, labels, cu, seq_slot)
+        n_opt = len(option_ids)
+        opt_a, _ = _i32(np.asarray(option_ids, np.int32) if n_opt else np.zeros(1, np.int32))
+        kind_a = None if seq_kind is None else np.ascontiguousarray(seq_kind, np.int32)
+        if kind_a is not None and len(kind_a) != len(keep[2]) - 1:
+            raise TstError("seq_kind needs one entry per sequence")
+        base_a = None if baseline_ids is None else np.ascontiguousarray(baseline_ids, np.int32)
+        if base_a is not None and len(base_a) != b.n_tokens:
+            raise TstError("baseline_ids needs one entry per token")
+        self._check(self.lib.tst_attribute_ig_async(self.h, C.byref(b), None if kind_a is None else _ptr(kind_a), _ptr(opt_a), n_opt,
+                                                    None if base_a is None else _ptr(base_a), int(n_steps)), "tst_attribute_ig_async")
+        self._pending_attr_ig = (int(b.n_tokens), int(b.n_seqs))
+
+    def attribute_ig_fetch(self):
+        """(ig [n_tokens], log_s [n_seqs], log_s_base [n_seqs]): per token the integrated gradient in the caller's token order; per sequence log s(x) of the real
+        prompt and of the baseline prompt. The ig of a sequence's tokens sum to log_s - log_s_base up to the quadrature error of n_steps."""
+        n_tok, n_seq = getattr(self, "_pending_attr_ig", None) or (1, 1)
+        ig, logs, logs_base = np.zeros(n_tok, np.float32), np.zeros(n_seq, np.float32), np.zeros(n_seq, np.float32)
+        self._check(self.lib.tst_attribute_ig_fetch(self.h, _ptr(ig), _ptr(logs), _ptr(logs_base)), "tst_attribute_ig_fetch")
+        self._pending_attr_ig = None
+        return ig, logs, logs_base
+
+    def attribute_ig(self, ids, labels, cu, baseline_ids, n_steps, seq_kind=None, option_ids=(), seq_slot=None):
+        self.attribute_ig_async(ids, labels, cu, baseline_ids, n_steps, seq_kind, option_ids, seq_slot)
+        return self.attribute_ig_fetch()
 
     def forward_logits(self, ids, cu, rows, seq_slot=None):
         b, keep = self._batch(ids, None, cu, seq_slot)

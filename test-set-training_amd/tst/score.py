@@ -9,6 +9,8 @@ only names s(x), so the definition is this build's and is frozen here):
 With attribution switched on (TrainArgs.attribute) a sample also carries WHICH prompt tokens its score rests on: the gradient of log s(x) with respect to every
 prompt token's embedding output, as gradient x input and as gradient norm (token_attribution; the definition is frozen in include/tst_hip.h
 tst_attribute_async). log s is differentiated rather than s so that the scale does not collapse for confident samples; d s = s d log s.
+With integrated gradients (token_ig; tst_attribute_ig_async) the prompt tokens instead share out, with sign, the change of log s(x) between a prompt of baseline
+tokens and the real one.
 
 With generation switched on (TrainArgs.generate) a sample also carries what the text-only model SAYS: its greedy continuation of the prompt
 (generated_answers), and gen_correct = that continuation starts with the reference answer's tokens. bias_scores does not change.
@@ -58,6 +60,34 @@ def token_attribution(samples, gxi, gnorm, logs):
         tot = float(n.astype(np.float64).sum())
         out.append(dict(gxi=g, gnorm=n, share=(n / tot if tot > 0 else np.zeros_like(n)).astype(np.float32), log_s=float(logs[i])))
         o += len(smp.ids)
+    return out
+
+
+def ig_baseline_ids(samples, baseline_id):
+    """baseline_ids of Context.attribute_ig for the samples of a batch (full sequences, in batch order): baseline_id on every prompt token, the token's own id
+    on the answer tokens -- those are not interpolated, so the teacher-forced answer stays what it is"""
+    out = []
+    for smp in samples:
+        row = np.asarray(smp.ids, np.int32).copy()
+        row[:smp.n_prompt] = baseline_id
+        out.append(row)
+    return np.concatenate(out) if out else np.zeros(0, np.int32)
+
+
+def token_ig(samples, ig, logs, logs_base):
+    """samples: the attributed batch in batch order (full sequences, as data.collate packs them); ig per token, logs / logs_base per sample as returned by
+    Context.attribute_ig. Returns per sample dict(ig: the prompt tokens' values, log_s, log_s_base, delta = sum of ig over ALL tokens of the sample
+    - (log_s - log_s_base): the completeness gap, 0 in the limit of many steps)."""
+    ig = np.asarray(ig, np.float32)
+    if len(ig) != sum(len(s.ids) for s in samples) or len(logs) != len(samples) or len(logs_base) != len(samples):
+        raise ValueError("token_ig: the arrays do not belong to this batch")
+    out, o = [], 0
+    for i, smp in enumerate(samples):
+        n = len(smp.ids)
+        total = float(ig[o:o + n].astype(np.float64).sum())
+        out.append(dict(ig=ig[o:o + smp.n_prompt].copy(), log_s=float(logs[i]), log_s_base=float(logs_base[i]),
+                        delta=total - (float(logs[i]) - float(logs_base[i]))))
+        o += n
     return out
 
 

@@ -44,9 +44,15 @@ class TrainArgs:
     # such a run's directory still resumes; tst.diagnose.run_fingerprint adds them when attribution is on. (dataclasses.replace does not carry them over.)
     attribute: InitVar[bool] = False
     attribute_top: InitVar[int] = 5
+    # integrated gradients on the held-out fold (off at 0 steps): every record gains `attr_ig` (include/tst_hip.h tst_attribute_ig_async), the prompt tokens walked
+    # from attribute_baseline_id to their own embeddings in attribute_ig midpoint steps, the answer tokens left as they are. Constructor arguments and attributes,
+    # NOT dataclass fields, for the reason above.
+    attribute_ig: InitVar[int] = 0
+    attribute_baseline_id: InitVar[int] = 0
 
-    def __post_init__(self, attribute, attribute_top):
+    def __post_init__(self, attribute, attribute_top, attribute_ig, attribute_baseline_id):
         self.attribute, self.attribute_top = bool(attribute), int(attribute_top)
+        self.attribute_ig, self.attribute_baseline_id = int(attribute_ig), int(attribute_baseline_id)
 
 
 def linear_lr(step, total, lr0, warmup=0):
@@ -296,19 +302,46 @@ def _attribute_async(ctx, batch, args: TrainArgs, seq_slot=None):
     ctx.attribute_async(ids, labels, cu, S.attribution_kinds(batch), args.option_ids, seq_slot)   # MCA and open samples in one batch
 
 
-def attribute_heldout(ctx, samples, args: TrainArgs):
+def _ig_async(ctx, batch, args: TrainArgs, seq_slot=None):
+    ids, labels, cu = D.collate(batch)
+    ctx.attribute_ig_async(ids, labels, cu, S.ig_baseline_ids(batch, args.attribute_baseline_id), args.attribute_ig, S.attribution_kinds(batch), args.option_ids,
+                           seq_slot)
+
+
+# what the three held-out drivers below run: (enqueue on a context, turn a fetched batch into per-sample dicts)
+_ATTR = (_attribute_async, lambda ctx, batch: S.token_attribution(batch, *ctx.attribute_fetch()))
+_IG = (_ig_async, lambda ctx, batch: S.token_ig(batch, *ctx.attribute_ig_fetch()))
+
+
+def attribute_ig_heldout(ctx, samples, args: TrainArgs):
+    """integrated gradients of log s(x) for every held-out sample (Context.attribute_ig: args.attribute_ig steps from a prompt of args.attribute_baseline_id);
+    returns tst.score.token_ig's dict per sample in input order. args.attribute_ig forward + backward passes and two forward passes per batch (measured: DESIGN.md section 14)."""
+    return attribute_heldout(ctx, samples, args, _IG)
+
+
+def attribute_ig_heldout_concurrent(ctxs, sample_sets, args: TrainArgs):
+    """attribute_ig_heldout for several resident folds (as attribute_heldout_concurrent)"""
+    return attribute_heldout_concurrent(ctxs, sample_sets, args, _IG)
+
+
+def attribute_ig_heldout_stacked(ctxs, sample_sets, args: TrainArgs):
+    """attribute_ig_heldout on stacked contexts (as attribute_heldout_stacked)"""
+    return attribute_heldout_stacked(ctxs, sample_sets, args, _IG)
+
+
+def attribute_heldout(ctx, samples, args: TrainArgs, how=_ATTR):
     """input-gradient attribution of log s(x) for every held-out sample (Context.attribute, batches of per_device_eval_batch_size); returns
     tst.score.token_attribution's dict per sample in input order. About one training forward + backward per batch."""
     bs = args.per_device_eval_batch_size
     out = []
     for b in range(0, len(samples), bs):
         batch = samples[b:b + bs]
-        _attribute_async(ctx, batch, args)
-        out += S.token_attribution(batch, *ctx.attribute_fetch())
+        how[0](ctx, batch, args)
+        out += how[1](ctx, batch)
     return out
 
 
-def attribute_heldout_concurrent(ctxs, sample_sets, args: TrainArgs):
+def attribute_heldout_concurrent(ctxs, sample_sets, args: TrainArgs, how=_ATTR):
     """attribute_heldout for several resident folds: batch b of every fold is enqueued before batch b-1's results are read."""
     bs = args.per_device_eval_batch_size
     outs = [[] for _ in ctxs]
@@ -316,7 +349,7 @@ def attribute_heldout_concurrent(ctxs, sample_sets, args: TrainArgs):
 
     def fetch(j):
         if pending[j] is not None:
-            outs[j] += S.token_attribution(pending[j], *ctxs[j].attribute_fetch())
+            outs[j] += how[1](ctxs[j], pending[j])
             pending[j] = None
 
     nb = max((len(smp) + bs - 1) // bs for smp in sample_sets) if sample_sets else 0
@@ -325,14 +358,14 @@ def attribute_heldout_concurrent(ctxs, sample_sets, args: TrainArgs):
             fetch(j)
             batch = smp[b * bs:(b + 1) * bs]
             if batch:
-                _attribute_async(c, batch, args)
+                how[0](c, batch, args)
                 pending[j] = batch
     for j in range(len(ctxs)):
         fetch(j)
     return outs
 
 
-def attribute_heldout_stacked(ctxs, sample_sets, args: TrainArgs):
+def attribute_heldout_stacked(ctxs, sample_sets, args: TrainArgs, how=_ATTR):
     """attribute_heldout on stacked contexts: batch b of all folds of a context is one attribution, every sequence under its own slot's adapters;
     returns the per-sample dicts per fold, in the order of sample_sets."""
     where = place_folds(len(sample_sets), ctxs)
@@ -344,7 +377,7 @@ def attribute_heldout_stacked(ctxs, sample_sets, args: TrainArgs):
     def fetch(j):
         if pending[j] is not None:
             parts = pending[j]   # [(fold position, samples)]
-            got = S.token_attribution([x for _, b in parts for x in b], *ctxs[j].attribute_fetch())
+            got = how[1](ctxs[j], [x for _, b in parts for x in b])
             o = 0
             for i, b in parts:
                 outs[i] += got[o:o + len(b)]
@@ -359,7 +392,7 @@ def attribute_heldout_stacked(ctxs, sample_sets, args: TrainArgs):
             parts = [(sl, i, x) for sl, i, x in parts if x]
             if parts:
                 seq_slot = np.concatenate([np.full(len(xs), sl, np.int32) for sl, _, xs in parts])
-                _attribute_async(c, [x for _, _, xs in parts for x in xs], args, seq_slot)
+                how[0](c, [x for _, _, xs in parts for x in xs], args, seq_slot)
                 pending[j] = [(i, xs) for _, i, xs in parts]
     for j in range(len(ctxs)):
         fetch(j)

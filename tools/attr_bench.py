@@ -11,7 +11,14 @@ handed to tst_set_stream; torch is used for the stream and the events only, and 
 and the ratio of the medians.
 Hit rate: a small LoRA model (--hit-model, default tiny; the recipe of tests/test_diagnostic_gpu.py) is fine-tuned on synthetic 4-way multiple-choice samples in
 which ONE prompt token (position 5) fixes the answer, then fresh samples of the same kind are attributed; reported is how often that token is the prompt's top-1 by gnorm (and by |gxi|), beside the chance
-rate 1 / prompt length and the model's accuracy on those samples. Reported, not asserted: no reference value exists."""
+rate 1 / prompt length and the model's accuracy on those samples. Reported, not asserted: no reference value exists.
+
+    python3 tools/attr_bench.py --ig [--ig-steps 16] [--out profiles/attr_ig_bench.json]
+
+The same two measurements for integrated gradients (tst_attribute_ig_async), same harness. Cost: Context.attribute_ig with --ig-steps steps (prompt tokens walked
+from token id 0, answer tokens kept) against --ig-steps calls of Context.attribute on the same batch, arms alternating; expected ratio (m + 2/3) / m -- the two
+passes without a backward cost about a third of a forward + backward each. Hit rate: on the same trained model, how often the planted token is the prompt's top-1
+by |ig|, beside gnorm's and |gxi|'s rates from the same run, and the mean completeness gap |delta| / |log s - log s_base| at --ig-steps and twice as many."""
 import argparse
 import json
 import os
@@ -22,7 +29,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "test-set-training_amd"))
 from tst import cli, data as D, lib, score as S  # noqa: E402
-from tst.trainer import TrainArgs, attribute_heldout, fine_tune, score_heldout  # noqa: E402
+from tst.trainer import TrainArgs, attribute_heldout, attribute_ig_heldout, fine_tune, score_heldout  # noqa: E402
 
 
 def cost(a):
@@ -49,6 +56,10 @@ def cost(a):
         return float(e0.elapsed_time(e1))
 
     arms = dict(attribute=lambda: ctx.attribute(ids, labels, cu, kinds, D.OPTION_IDS), forward_backward=lambda: ctx.forward_backward(ids, labels, cu))
+    if a.ig:
+        base = S.ig_baseline_ids(samples, 0)
+        arms = {"attribute_ig": lambda: ctx.attribute_ig(ids, labels, cu, base, a.ig_steps, kinds, D.OPTION_IDS),
+                "m_x_attribute": lambda: [ctx.attribute(ids, labels, cu, kinds, D.OPTION_IDS) for _ in range(a.ig_steps)]}
     for fn in arms.values():
         fn()
         fn()
@@ -61,7 +72,12 @@ def cost(a):
     res = dict(model=a.model, layers=cfg["num_layers"], pairs=a.pairs, tokens=int(len(ids)), labelled=int((labels != -100).sum()), rounds=a.rounds, lora_r=16, tile_policy=3,
                method="HIP events on the context's stream around each call, arms alternating, 2 untimed warm-up calls per arm",
                ms={k: dict(median=float(np.median(t)), min=float(min(t)), max=float(max(t)), windows=[round(x, 3) for x in t]) for k, t in times.items()})
-    res["ratio_attribute_over_forward_backward"] = res["ms"]["attribute"]["median"] / res["ms"]["forward_backward"]["median"]
+    if a.ig:
+        res["ig_steps"] = a.ig_steps
+        res["ratio_attribute_ig_over_m_x_attribute"] = res["ms"]["attribute_ig"]["median"] / res["ms"]["m_x_attribute"]["median"]
+        res["expected_ratio"] = (a.ig_steps + 2.0 / 3.0) / a.ig_steps
+    else:
+        res["ratio_attribute_over_forward_backward"] = res["ms"]["attribute"]["median"] / res["ms"]["forward_backward"]["median"]
     return res
 
 
@@ -76,11 +92,24 @@ def hits(a):
     fine_tune(ctx, train, args)
     _, _, correct = score_heldout(ctx, held, args)
     attr = attribute_heldout(ctx, held, args)
+    igs = {}
+    if a.ig:
+        for m in (a.ig_steps, 2 * a.ig_steps):
+            args.attribute_ig, args.attribute_baseline_id = m, 0
+            igs[m] = attribute_ig_heldout(ctx, held, args)
     ctx.close()
     top_n = np.array([int(np.argmax(x["gnorm"])) for x in attr])
     top_x = np.array([int(np.argmax(np.abs(x["gxi"]))) for x in attr])
     share = np.array([float(x["share"][5]) for x in attr])
-    return dict(model=a.hit_model, train=a.hit_train, heldout=a.hit_heldout, epochs=a.hit_epochs, lr=a.hit_lr, planted_position=5, accuracy=float(np.mean(correct)),
+    extra = {}
+    if a.ig:
+        top_i = np.array([int(np.argmax(np.abs(x["ig"]))) for x in igs[a.ig_steps]])
+        extra = dict(baseline_id=0, top1_by_abs_ig=float((top_i == 5).mean()),
+                     mean_ig_of_planted_token=float(np.mean([x["ig"][5] for x in igs[a.ig_steps]])),
+                     mean_abs_delta_over_abs_dJ={str(m): float(np.mean([abs(x["delta"]) / max(abs(x["log_s"] - x["log_s_base"]), 1e-12) for x in v])) for m, v in igs.items()},
+                     median_abs_delta_over_abs_dJ={str(m): float(np.median([abs(x["delta"]) / max(abs(x["log_s"] - x["log_s_base"]), 1e-12) for x in v])) for m, v in igs.items()},
+                     mean_abs_dJ=float(np.mean([abs(x["log_s"] - x["log_s_base"]) for x in igs[a.ig_steps]])))
+    return dict(**extra, model=a.hit_model, train=a.hit_train, heldout=a.hit_heldout, epochs=a.hit_epochs, lr=a.hit_lr, planted_position=5, accuracy=float(np.mean(correct)),
                 top1_by_gnorm=float((top_n == 5).mean()), top1_by_abs_gxi=float((top_x == 5).mean()), mean_share_of_planted_token=float(share.mean()),
                 chance=float(np.mean([1.0 / s.n_prompt for s in held])))
 
@@ -98,8 +127,11 @@ def main():
     ap.add_argument("--hit-lr", type=float, default=2e-3)
     ap.add_argument("--skip-cost", action="store_true")
     ap.add_argument("--skip-hits", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attr_bench.json"))
+    ap.add_argument("--ig", action="store_true", help="measure integrated gradients (Context.attribute_ig) instead; default --out profiles/attr_ig_bench.json")
+    ap.add_argument("--ig-steps", type=int, default=16)
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "attr_ig_bench.json" if a.ig else "attr_bench.json")
     if not a.skip_cost:
         # torch supplies the stream and the events of the cost measurement; its HIP runtime has to be live BEFORE libtst_hip.so is loaded
         # (tests/test_torch_coexist_gpu.py: the library then runs on the runtime torch loaded)

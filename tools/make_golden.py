@@ -9,6 +9,7 @@ It never travels to the GPU box as a dependency: tests read the .npz files.
     python tools/make_golden.py            # rewrites tests/golden/*.npz
     python tools/make_golden.py qwen3      # one family only (here: the Qwen3 fixtures, tests/qwen3_inputs.py)
     python tools/make_golden.py attr       # the token-attribution fixtures (tests/attribution_inputs.py)
+    python tools/make_golden.py ig         # the integrated-gradients fixtures (tests/ig_inputs.py)
 """
 import os
 import sys
@@ -581,10 +582,9 @@ def _inject_lora_any(cfg, m, lora):
             setattr(parent, leaf, LoraConv1D(getattr(parent, leaf), lora[key + ".lora_A"], lora[key + ".lora_B"], GI.LORA_ALPHA / GI.LORA_R))
 
 
-def run_attr(tag):
-    """attr_<tag>.npz: gradient x input and gradient norm of J = sum_i log s(x_i) w.r.t. the embedding-layer output, from the HF model fed inputs_embeds with
-    requires_grad. Per fixture set (AI.SETS) and adapter set (AI.ADAPTERS): ref_* from model.double(), hf32_* / hf_bf16_* from model.float() / .bfloat16(),
-    floor32 / floor16 = per output the max over sequences of max_t |x - ref| / max_t |ref|. Sequences run one at a time: they do not interact."""
+def _attr_kit(tag):
+    """what run_attr and run_ig share: the batch, the HF models of the three precisions (the fp64 one as the reference takes it) and J of one sequence"""
+    import types
     import attribution_inputs as AI
     cfg, make_w = AI.TAGS[tag]
     gpt2 = cfg.get("arch") == "gpt2"
@@ -625,6 +625,16 @@ def run_attr(tag):
         if gpt2:
             return m.transformer.wte.weight[t].detach().clone(), m.transformer.wpe.weight[: len(t)].detach().clone()
         return m.model.embed_tokens.weight[t].detach().clone(), None
+
+    return types.SimpleNamespace(AI=AI, cfg=cfg, gpt2=gpt2, ids=ids, labels=labels, cu=cu, opt=opt, S=S, model=model, J_of=J_of, embed_parts=embed_parts)
+
+
+def run_attr(tag):
+    """attr_<tag>.npz: gradient x input and gradient norm of J = sum_i log s(x_i) w.r.t. the embedding-layer output, from the HF model fed inputs_embeds with
+    requires_grad. Per fixture set (AI.SETS) and adapter set (AI.ADAPTERS): ref_* from model.double(), hf32_* / hf_bf16_* from model.float() / .bfloat16(),
+    floor32 / floor16 = per output the max over sequences of max_t |x - ref| / max_t |ref|. Sequences run one at a time: they do not interact."""
+    kit = _attr_kit(tag)
+    AI, gpt2, ids, labels, cu, S, model, J_of, embed_parts = kit.AI, kit.gpt2, kit.ids, kit.labels, kit.cu, kit.S, kit.model, kit.J_of, kit.embed_parts
 
     def attribute(m, kinds):
         gxi, gnorm, logs = [], [], []
@@ -675,6 +685,81 @@ def run_attr(tag):
     np.savez_compressed(os.path.join(OUT, f"attr_{tag}.npz"), **res)
 
 
+# ------------------------------------------------------------------------------------------------ integrated gradients (include/tst_hip.h tst_attribute_ig_async)
+def run_ig(tag):
+    """ig_<tag>.npz: integrated gradients of J = sum_i log s(x_i) from a baseline prompt to the real one (midpoint rule, IG.STEPS steps), from the HF models of
+    run_attr. Per fixture set, baseline pattern (IG.PATTERNS) and adapter set: ref_ig / ref_logs / ref_logs_base from the fp64 model, hf32_* / hf_bf16_* from
+    model.float() / .bfloat16() -- the interpolation in fp32 from the model-dtype table rows, rounded once: the library's contract --, floor32 / floor16 = the max
+    over sequences of max_t |ig - ref| / max_t |ref|; ref_ig64 / delta_ref64 / ref_gap64 = the reference at IG.STEPS_FINE steps, its completeness gap
+    sum_t ig - (J(e) - J(b)) per sequence, and that gap as a fraction of |J(e) - J(b)| (nan where that is below 0.05).
+    Self-check: ref_gap64 <= 2 % everywhere; a case that misses it is checked again at twice the steps (ref_gap128 <= 2 %, stored for that case only), or nothing
+    is written."""
+    import ig_inputs as IG
+    kit = _attr_kit(tag)
+    AI, gpt2, ids, labels, cu, S, model, J_of = kit.AI, kit.gpt2, kit.ids, kit.labels, kit.cu, kit.S, kit.model, kit.J_of
+
+    def table(m):
+        return (m.transformer.wte if gpt2 else m.model.embed_tokens).weight.detach()
+
+    def ig_of(m, kinds, base_ids, steps):
+        """(ig [T], logs [S], logs_base [S]) in float64; the per-step products and the sum over the steps are taken in fp64 whatever the model's dtype"""
+        E = table(m)
+        wide = torch.float64 if E.dtype == torch.float64 else torch.float32
+        out, logs, logs_base = [], [], []
+        for s in range(S):
+            t = torch.from_numpy(ids[cu[s]:cu[s + 1]].astype(np.int64))
+            bt = torch.from_numpy(base_ids[cu[s]:cu[s + 1]].astype(np.int64))
+            lab = labels[cu[s]:cu[s + 1]]
+            e, b = E[t].clone(), E[bt].clone()
+            same = (t == bt)[:, None]
+            diff = e.double() - b.double()
+            with torch.no_grad():
+                logs.append(float(J_of(m, e, lab, kinds[s])))
+                logs_base.append(float(J_of(m, b, lab, kinds[s])))
+            acc = torch.zeros(len(t), dtype=torch.float64)
+            for k in range(1, steps + 1):
+                alpha = float(IG.alpha(k, steps))
+                x = torch.where(same, e, (b.to(wide) + alpha * (e.to(wide) - b.to(wide))).to(E.dtype)).detach().requires_grad_(True)
+                g, = torch.autograd.grad(J_of(m, x, lab, kinds[s]), x)
+                acc += (g.double() * diff).sum(-1)
+            out.append((acc / steps).numpy())
+        return np.concatenate(out), np.array(logs), np.array(logs_base)
+
+    res = dict(option_ids=AI.option_ids(tag))
+    for aname, adapter in AI.ADAPTERS.items():
+        m64, m32, m16 = model(adapter, torch.float64), model(adapter, torch.float32), model(adapter, torch.bfloat16)
+        for sname, kinds in AI.SETS.items():
+            for pname in IG.PATTERNS:
+                key = f"{sname}/{pname}/{aname}/"
+                base_ids = IG.baseline_ids(tag, pname)
+                ref = ig_of(m64, kinds, base_ids, IG.STEPS)
+                fine = ig_of(m64, kinds, base_ids, IG.STEPS_FINE)
+                dJ = fine[1] - fine[2]
+                delta = np.array([fine[0][cu[s]:cu[s + 1]].sum() for s in range(S)]) - dJ
+                gap = np.where(np.abs(dJ) >= 0.05, np.abs(delta) / np.maximum(np.abs(dJ), 1e-300), np.nan)
+                if np.nanmax(gap) > 0.02:   # the quadrature has not converged there yet: the self-check moves to twice the steps, the bound stays
+                    finer = ig_of(m64, kinds, base_ids, 2 * IG.STEPS_FINE)
+                    delta2 = np.array([finer[0][cu[s]:cu[s + 1]].sum() for s in range(S)]) - dJ
+                    gap2 = np.where(np.abs(dJ) >= 0.05, np.abs(delta2) / np.maximum(np.abs(dJ), 1e-300), np.nan)
+                    print(f"ig_{tag} {key}: gap at m = {IG.STEPS_FINE} {gap}; at m = {2 * IG.STEPS_FINE} {gap2}")
+                    if np.nanmax(gap2) > 0.02:
+                        raise SystemExit(f"ig_{tag} {key}: the fp64 reference misses completeness at m = {2 * IG.STEPS_FINE} by {gap2} of |dJ| = {np.abs(dJ)}: nothing written")
+                    res[key + "ref_gap128"] = gap2
+                res[key + "ref_ig"], res[key + "ref_logs"], res[key + "ref_logs_base"] = ref
+                res[key + "ref_ig64"], res[key + "delta_ref64"], res[key + "ref_gap64"] = fine[0], delta, gap
+                for pre, m in (("hf32", m32), ("hf_bf16", m16)):
+                    got = ig_of(m, kinds, base_ids, IG.STEPS)
+                    res[key + pre + "_ig"], res[key + pre + "_logs"], res[key + pre + "_logs_base"] = got
+                    res[key + ("floor32" if pre == "hf32" else "floor16")] = np.float64(AI.seq_dev(got[0], ref[0], cu).max())
+                print(f"ig_{tag} {key}: gap64 {np.round(gap, 5)} dJ {np.round(dJ, 4)} floor32 {res[key + 'floor32']:.2e} floor16 {res[key + 'floor16']:.4f}", flush=True)
+    for sname in AI.SETS:
+        for pname in IG.PATTERNS:
+            res[f"{sname}/{pname}/l99_vs_l7"] = AI.seq_dev(res[f"{sname}/{pname}/l7/ref_ig"], res[f"{sname}/{pname}/l99/ref_ig"], cu)
+            f16 = max(res[f"{sname}/{pname}/l99/floor16"], res[f"{sname}/{pname}/l7/floor16"])
+            print(f"ig_{tag} {sname}/{pname}: l99 vs l7 per sequence {res[f'{sname}/{pname}/l99_vs_l7']}; 4 x floor16 = {4 * f16}")
+    np.savez_compressed(os.path.join(OUT, f"ig_{tag}.npz"), **res)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = set(sys.argv[1:]) or {"ops", "kfold", "llama", "gpt2", "strict"}   # e.g. `python tools/make_golden.py gpt2` regenerates only that family
@@ -702,6 +787,9 @@ if __name__ == "__main__":
     if "attr" in which:   # the token-attribution fixtures only (attr_<tag>.npz, tests/attribution_inputs.py): not part of the default set
         for tag in ("tiny", "tiny2", "qwen", "qwen3", "gpt2"):
             run_attr(tag)
+    if "ig" in which:   # the integrated-gradients fixtures only (ig_<tag>.npz, tests/ig_inputs.py): not part of the default set
+        for tag in ("tiny", "tiny2", "qwen", "qwen3", "gpt2"):
+            run_ig(tag)
     if "rope" in which or "strict" in which:
         run_rope_scaling()
         run_strict(GI.TINY_RS_CFG, "tiny_rs")
