@@ -136,6 +136,33 @@ int tst_k_attn_decode(const void* q, int64_t ldq, const void* kcache, const void
                       int Hkv, int dh, float scale, int64_t cap_rows);
 int tst_k_adamw(float* p, const float* g, float* m, float* v, int64_t n, float max_norm, float lr, float beta1, float beta2, float eps, float wd,
                 int step, float* norm_coef_out /* device [2] */, float* partial_ws /* device [256] */);
+/* the optimizer kernels of csrc/optim.hip one by one; every pointer is a device pointer unless stated, every hook synchronises.
+ * clip_coef = sumsq_partial + clip_finalize as the engine chains them: out2 = {||g||, min(1, max_norm / (||g|| + 1e-6))} (coefficient 1 for max_norm <= 0),
+ * 1 <= nparts <= 4096 partials in partial_ws (clamped to the work). g must be 16-byte aligned in clip_coef and sumsq_partial (TST_EINVAL, nothing launched).
+ * sumsq_partial: partial[0 .. nparts) = the workgroups' sums of squares (an idle workgroup writes 0). clip_finalize: out2 from nparts partials.
+ * sum_partials: out1[0] = their sum; clip_from_sumsq: out2 from a sum of squares. */
+int tst_k_clip_coef(const float* g, int64_t n, float max_norm, float* partial_ws, int nparts, float* out2);
+int tst_k_sumsq_partial(const float* g, int64_t n, float* partial, int nparts);
+int tst_k_clip_finalize(const float* partial, int nparts, float max_norm, float* out2);
+int tst_k_sum_partials(const float* partial, int nparts, float* out1);
+int tst_k_clip_from_sumsq(const float* sumsq1, float max_norm, float* out2);
+/* one AdamW step on flat buffers, no clip pass of its own: clip = device {norm, coef} (the gradient is scaled by coef) or NULL; bias corrections from `step` in
+ * host double precision as tst_k_adamw; shadow (may be NULL) also receives the new parameters, rounded to bf16 (f32 = 0) or as fp32 (f32 = 1).
+ * adamw_matrix: the same on a row-major [rows, cols] matrix (multiples of 64), shadow [rows, cols] and shadowT [cols, rows] both required. */
+int tst_k_adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, const float* clip, float lr, float beta1, float beta2, float eps, float wd, int step,
+                     void* shadow, int f32);
+int tst_k_adamw_matrix(float* p, const float* g, float* m, float* v, int rows, int cols, const float* clip, float lr, float beta1, float beta2, float eps, float wd,
+                       int step, void* shadow, void* shadowT, int f32);
+int tst_k_grad_accumulate(float* acc, const float* g, int64_t n, int first);   /* acc = first ? g : acc + g */
+/* LoRA pack / unpack of ngroups <= 16 module groups in ONE launch (layout: csrc/optim.hip above lora_pack_tiled_kernel). Host arrays describe group i:
+ * dims[5 i ..] = {din, dout, r, nmod, nslot} (din, dout multiples of 64; r <= 64; nmod <= 4 enabled modules; nslot <= 8), seg_row0 / seg_row1[4 i + m] = output rows
+ * [row0, row1) of enabled module m, a_off / b_off[32 i + slot nmod + m] = float offsets of A [r, din] / B [rows, r] in master resp. grad (multiples of 4),
+ * scale[i], bufs[6 i ..] = device {Ag [RP, din], AgT [din, RP], Bg [dout, RP], BgT [RP, dout], dAg [RP, din] fp32, dBg [dout, RP] fp32}, RP = nslot nmod r rounded
+ * up to 64; the first four hold bf16 (f32 = 0) or fp32 (f32 = 1). pack reads master and writes Ag .. BgT; unpack reads dAg, dBg and writes the groups' ranges of grad. */
+int tst_k_lora_pack(int ngroups, const int32_t* dims, const int32_t* seg_row0, const int32_t* seg_row1, const int64_t* a_off, const int64_t* b_off,
+                    const float* scale, void* const* bufs, const float* master, int f32);
+int tst_k_lora_unpack_grad(int ngroups, const int32_t* dims, const int32_t* seg_row0, const int32_t* seg_row1, const int64_t* a_off, const int64_t* b_off,
+                           const float* scale, void* const* bufs, float* grad, int f32);
 int tst_k_tr_probe(void* out_u16_64x8, int d0);
 /* diagnostic: while a device buffer of 2 x 256 uint64 is set, the ping-pong contraction (variant 5) runs a build that
  * stamps s_memtime after each main-loop barrier of workgroup 0 (waves 0 and 4) into it; NULL restores the plain kernel */

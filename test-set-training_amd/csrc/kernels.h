@@ -214,6 +214,8 @@ template <typename AT> int lora_unpack_grad(hipStream_t st, const LoraGroupDescT
 int rank_mask(hipStream_t st, bf16_t* u, int ld, int T, int width, int nslot, SlotEnds ends);
 
 int grad_accumulate(hipStream_t st, float* acc, const float* g, long n, int first);   // acc = first ? g : acc + g
+// grad_clip_coef / sumsq_partial read g in 16-byte pieces without a scalar form: g must be 16-byte aligned (TST_EINVAL otherwise, nothing is launched). Every
+// range the engine hands over is: ZeRO shards, stacked slots and layer regions start at multiples of 64 floats (host_logic.h zero_shard pads to 64 * ranks).
 int grad_clip_coef(hipStream_t st, const float* g, long n, float max_norm, float* partial_ws, int nparts, float* out2);
 int sumsq_partial(hipStream_t st, const float* g, long n, float* partial, int nparts);       // stage 1 alone: partial[0..nparts)
 int clip_finalize(hipStream_t st, const float* partial, int nparts, float max_norm, float* out2);  // stage 2 alone

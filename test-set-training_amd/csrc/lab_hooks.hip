@@ -11,6 +11,52 @@
 #include "common.h"
 #include "kernels.h"
 
+namespace {
+// tst_k_lora_pack (master != NULL) / tst_k_lora_unpack_grad (grad != NULL): the descriptors as engine.hip add_group / build_ctx fill them (nseg = nslot * nmod,
+// RP = nseg * r rounded up to 64), uploaded, one launch with the engine's grid bounds (longest axis resp. most padded elements of a group), synchronised, freed.
+// What the kernels rely on is checked here: 64-wide tiles along din / dout, 16-byte reads of the A master always and of the B master on the r % 8 == 0 path.
+template <typename AT>
+int lora_lab(int ngroups, const int32_t* dims, const int32_t* seg_row0, const int32_t* seg_row1, const int64_t* a_off, const int64_t* b_off, const float* scale,
+             void* const* bufs, const float* master, float* grad) {
+  if (ngroups < 1 || ngroups > 16 || !dims || !seg_row0 || !seg_row1 || !a_off || !b_off || !scale || !bufs || (!master && !grad)) return TST_EINVAL;
+  if (master && (((unsigned long long)master) & 15ull)) return TST_EINVAL;
+  std::vector<LoraGroupDescT<AT>> descs((size_t)ngroups);
+  long max_long = 0, max_elems = 0;
+  for (int i = 0; i < ngroups; ++i) {
+    LoraGroupDescT<AT>& d = descs[(size_t)i];
+    memset(&d, 0, sizeof(d));
+    d.din = dims[5 * i]; d.dout = dims[5 * i + 1]; d.r = dims[5 * i + 2]; d.nmod = dims[5 * i + 3]; d.nslot = dims[5 * i + 4];
+    if (d.din < 64 || (d.din & 63) || d.dout < 64 || (d.dout & 63) || d.r < 1 || d.r > 64 || d.nmod < 1 || d.nmod > 4 || d.nslot < 1 || d.nslot > TST_MAX_STACK)
+      return TST_EINVAL;
+    d.nseg = d.nslot * d.nmod;
+    d.RP = (d.nseg * d.r + 63) / 64 * 64;
+    d.scale = scale[i];
+    for (int m = 0; m < d.nmod; ++m) {
+      d.seg_row0[m] = seg_row0[4 * i + m]; d.seg_row1[m] = seg_row1[4 * i + m];
+      if (d.seg_row0[m] < 0 || d.seg_row1[m] <= d.seg_row0[m] || d.seg_row1[m] > d.dout) return TST_EINVAL;
+    }
+    for (int s = 0; s < d.nseg; ++s) {
+      d.a_off[s] = (long)a_off[32 * i + s]; d.b_off[s] = (long)b_off[32 * i + s];
+      if (d.a_off[s] < 0 || d.b_off[s] < 0 || (d.a_off[s] & 3) || (d.b_off[s] & 3)) return TST_EINVAL;
+    }
+    for (int b = 0; b < 6; ++b)
+      if (!bufs[6 * i + b]) return TST_EINVAL;
+    d.Ag = (AT*)bufs[6 * i]; d.AgT = (AT*)bufs[6 * i + 1]; d.Bg = (AT*)bufs[6 * i + 2]; d.BgT = (AT*)bufs[6 * i + 3];
+    d.dAg = (float*)bufs[6 * i + 4]; d.dBg = (float*)bufs[6 * i + 5];
+    max_long = std::max(max_long, (long)std::max(d.din, d.dout));
+    max_elems = std::max(max_elems, (long)d.RP * d.din + (long)d.dout * d.RP);
+  }
+  LoraGroupDescT<AT>* dev = nullptr;
+  const size_t bytes = descs.size() * sizeof(LoraGroupDescT<AT>);
+  if (hipMalloc((void**)&dev, bytes) != hipSuccess) return TST_ENOMEM;
+  int rc = hipMemcpy(dev, descs.data(), bytes, hipMemcpyHostToDevice) == hipSuccess ? TST_OK : TST_EHIP;
+  if (rc == TST_OK) rc = master ? lora_pack<AT>(nullptr, dev, ngroups, master, max_long) : lora_unpack_grad<AT>(nullptr, dev, ngroups, grad, max_elems);
+  if (hipDeviceSynchronize() != hipSuccess) rc = TST_EHIP;
+  (void)hipFree(dev);
+  return rc;
+}
+}  // namespace
+
 extern "C" {
 
 int tst_dev_alloc(void** dptr, int64_t bytes) { return (dptr && hipMalloc(dptr, (size_t)(bytes > 0 ? bytes : 16)) == hipSuccess) ? TST_OK : TST_ENOMEM; }
@@ -291,6 +337,40 @@ int tst_k_adamw(float* p, const float* g, float* m, float* v, int64_t n, float m
   if (rc != TST_OK) return rc;
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   return adamw_step<bf16_t>(nullptr, p, g, m, v, n, norm_coef_out, lr, beta1, beta2, eps, wd, (float)bc1, (float)sqrt(bc2), nullptr);
+}
+// ---- the optimizer kernels one by one (optim.hip); a hook launches, synchronises and returns the library's status
+static int synced(int rc) { return hipDeviceSynchronize() == hipSuccess ? rc : TST_EHIP; }
+int tst_k_clip_coef(const float* g, int64_t n, float max_norm, float* partial_ws, int nparts, float* out2) {
+  return synced(grad_clip_coef(nullptr, g, (long)n, max_norm, partial_ws, nparts, out2));
+}
+int tst_k_sumsq_partial(const float* g, int64_t n, float* partial, int nparts) { return synced(sumsq_partial(nullptr, g, (long)n, partial, nparts)); }
+int tst_k_clip_finalize(const float* partial, int nparts, float max_norm, float* out2) { return synced(clip_finalize(nullptr, partial, nparts, max_norm, out2)); }
+int tst_k_sum_partials(const float* partial, int nparts, float* out1) { return synced(sum_partials(nullptr, partial, nparts, out1)); }
+int tst_k_clip_from_sumsq(const float* sumsq1, float max_norm, float* out2) { return synced(clip_from_sumsq(nullptr, sumsq1, max_norm, out2)); }
+int tst_k_adamw_flat(float* p, const float* g, float* m, float* v, int64_t n, const float* clip, float lr, float beta1, float beta2, float eps, float wd, int step,
+                     void* shadow, int f32) {
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  return synced(f32 ? adamw_step<float>(nullptr, p, g, m, v, (long)n, clip, lr, beta1, beta2, eps, wd, (float)bc1, (float)sqrt(bc2), (float*)shadow)
+                    : adamw_step<bf16_t>(nullptr, p, g, m, v, (long)n, clip, lr, beta1, beta2, eps, wd, (float)bc1, (float)sqrt(bc2), (bf16_t*)shadow));
+}
+int tst_k_adamw_matrix(float* p, const float* g, float* m, float* v, int rows, int cols, const float* clip, float lr, float beta1, float beta2, float eps, float wd,
+                       int step, void* shadow, void* shadowT, int f32) {
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  return synced(f32 ? adamw_step_matrix<float>(nullptr, p, g, m, v, rows, cols, clip, lr, beta1, beta2, eps, wd, (float)bc1, (float)sqrt(bc2), (float*)shadow,
+                                               (float*)shadowT)
+                    : adamw_step_matrix<bf16_t>(nullptr, p, g, m, v, rows, cols, clip, lr, beta1, beta2, eps, wd, (float)bc1, (float)sqrt(bc2), (bf16_t*)shadow,
+                                                (bf16_t*)shadowT));
+}
+int tst_k_grad_accumulate(float* acc, const float* g, int64_t n, int first) { return synced(grad_accumulate(nullptr, acc, g, (long)n, first)); }
+int tst_k_lora_pack(int ngroups, const int32_t* dims, const int32_t* seg_row0, const int32_t* seg_row1, const int64_t* a_off, const int64_t* b_off,
+                    const float* scale, void* const* bufs, const float* master, int f32) {
+  return f32 ? lora_lab<float>(ngroups, dims, seg_row0, seg_row1, a_off, b_off, scale, bufs, master, nullptr)
+             : lora_lab<bf16_t>(ngroups, dims, seg_row0, seg_row1, a_off, b_off, scale, bufs, master, nullptr);
+}
+int tst_k_lora_unpack_grad(int ngroups, const int32_t* dims, const int32_t* seg_row0, const int32_t* seg_row1, const int64_t* a_off, const int64_t* b_off,
+                           const float* scale, void* const* bufs, float* grad, int f32) {
+  return f32 ? lora_lab<float>(ngroups, dims, seg_row0, seg_row1, a_off, b_off, scale, bufs, nullptr, grad)
+             : lora_lab<bf16_t>(ngroups, dims, seg_row0, seg_row1, a_off, b_off, scale, bufs, nullptr, grad);
 }
 int tst_k_tr_probe(void* out_u16_64x8, int d0) { return tr_probe(nullptr, (unsigned short*)out_u16_64x8, d0); }
 int tst_k_gemm_pp_stamps(void* dev_u64_2x1024) { gemm_pp_set_stamps((unsigned long long*)dev_u64_2x1024); return TST_OK; }

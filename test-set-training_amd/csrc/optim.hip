@@ -323,6 +323,8 @@ inline int nblocks(long work, int cap) {
   if (b > cap) b = cap;
   return (int)b;
 }
+// sumsq_partial_kernel has no scalar form for an unaligned g (kernels.h): the host refuses it
+inline bool aligned16(const void* p) { return (((unsigned long long)p) & 15ull) == 0; }
 
 // gradient accumulation (HF/trainer.py:1740-1758: backward of every micro-batch adds into .grad): acc = first ? g : acc + g
 __global__ __launch_bounds__(256) void grad_accumulate_kernel(float* __restrict__ acc, const float* __restrict__ g, long n, int first) {
@@ -345,7 +347,7 @@ int grad_accumulate(hipStream_t st, float* acc, const float* g, long n, int firs
 }
 
 int grad_clip_coef(hipStream_t st, const float* g, long n, float max_norm, float* partial_ws, int nparts, float* out2) {
-  if (nparts < 1 || nparts > 4096) return TST_EINVAL;
+  if (nparts < 1 || nparts > 4096 || !aligned16(g)) return TST_EINVAL;
   // one block per partial; a full fine-tune streams 32 GB of gradients here: 256 blocks reached 2.3 TB/s, 4096 fill the chip
   const long want = (n / 4 + 255) / 256;
   if (want < nparts) nparts = want < 1 ? 1 : (int)want;
@@ -355,7 +357,7 @@ int grad_clip_coef(hipStream_t st, const float* g, long n, float max_norm, float
 }
 // the two stages of grad_clip_coef on their own (full fine-tune: the weight-gradient contractions leave their own partial sums)
 int sumsq_partial(hipStream_t st, const float* g, long n, float* partial, int nparts) {
-  if (nparts < 1 || n <= 0) return TST_EINVAL;
+  if (nparts < 1 || n <= 0 || !aligned16(g)) return TST_EINVAL;
   hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nparts), dim3(256), 0, st, g, n, partial);
   return hipGetLastError() == hipSuccess ? TST_OK : TST_EHIP;
 }
@@ -376,7 +378,8 @@ int adamw_step(hipStream_t st, float* p, const float* g, float* m, float* v, lon
                float wd, float bc1, float bc2_sqrt, AT* shadow) {
   if (n <= 0) return TST_OK;
   // 2 pieces in flight per lane and array; TST_ADAMW_NT = 1 / 0 non-temporal accesses on / off (A/B switch; the same arithmetic on the same elements in
-  // either form: bit-identical results). Default: non-temporal for the full fine-tune's 30 B/param stream (shadow != nullptr) -- measured on config 3, one GPU,
+  // either form: bit-identical results PER ELEMENT TYPE AT -- the bf16_t and the float instance differ from each other in the last bit of m on a few per cent of
+  // the second piece's elements, profiles/optim_kernel_parity.txt; a context never mixes the two). Default: non-temporal for the full fine-tune's 30 B/param stream (shadow != nullptr) -- measured on config 3, one GPU,
   // two rounds: 23.87 QA/s (1 piece, default policy) | 24.29 (1, nt) | 24.51 (2, nt); unrolling alone changes nothing (profiles/r05_full_adamw_ab.txt).
   constexpr int unroll = 2;
   static const int nt_env = [] { const char* e = getenv("TST_ADAMW_NT"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();

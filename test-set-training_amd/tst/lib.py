@@ -199,6 +199,16 @@ LAB_SIGNATURES = {
     "tst_k_kv_append_f32": (C.c_int, [_P, _L, _I, _P, _P, _P, _I, _I, _I, _L]),
     "tst_k_attn_decode_f32": (C.c_int, [_P, _L, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _F, _L]),
     "tst_k_adamw": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _I, _P, _P]),
+    "tst_k_clip_coef": (C.c_int, [_P, _L, _F, _P, _I, _P]),
+    "tst_k_sumsq_partial": (C.c_int, [_P, _L, _P, _I]),
+    "tst_k_clip_finalize": (C.c_int, [_P, _I, _F, _P]),
+    "tst_k_sum_partials": (C.c_int, [_P, _I, _P]),
+    "tst_k_clip_from_sumsq": (C.c_int, [_P, _F, _P]),
+    "tst_k_adamw_flat": (C.c_int, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _I, _P, _I]),
+    "tst_k_adamw_matrix": (C.c_int, [_P, _P, _P, _P, _I, _I, _P, _F, _F, _F, _F, _F, _I, _P, _P, _I]),
+    "tst_k_grad_accumulate": (C.c_int, [_P, _P, _L, _I]),
+    "tst_k_lora_pack": (C.c_int, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
+    "tst_k_lora_unpack_grad": (C.c_int, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "tst_k_tr_probe": (C.c_int, [_P, _I]),
     "tst_k_gemm_pp_stamps": (C.c_int, [_P]),
     "tst_k_gemm_bench": (C.c_int, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F)]),
