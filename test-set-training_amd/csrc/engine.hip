@@ -298,23 +298,21 @@ struct tst_ctx {
   std::vector<int> gen_eos;
   // Token attribution (tst_attribute_async; kernels in attribute.hip, row weights and the fetch side in host_logic.h). Allocated by the first attribution of the
   // context. attr_dev = row weights [Rmax] | row kinds [Rmax] | option ids [256] | gxi [Tmax] | gnorm [Tmax] (4-byte words); h_attr = the pinned staging image of the
-  // first three, then gxi | gnorm | row statistics [Rmax * 4] of the pending attribution. attr_pass: backward() runs for an attribution (seeded by attr_seed, the
-  // gradient of layer 0's input formed in LoRA contexts too, no embedding gradient). grad_stale: the flat gradient no longer holds a training step's gradient.
+  // first three, then gxi | gnorm | row statistics [Rmax * 4] of the pending attribution. forward() and backward() take the pass of an attribution as their AttrPass
+  // argument (below). grad_stale: the flat gradient no longer holds a training step's gradient.
   float* attr_dev = nullptr;
   float* h_attr = nullptr;
   hipEvent_t attr_evt = nullptr;   // recorded behind the result copies: tst_attribute_fetch waits for it, not for the stream
   int attr_S = -1, attr_nopt = 0;  // pending attribution (-1: none)
-  bool attr_pass = false, grad_stale = false;
+  bool grad_stale = false;
   tsthost::AttrPlan attr_plan;
   std::vector<int> attr_cu_dev, attr_cu_src;
   // Integrated gradients (tst_attribute_ig_async): the same pending slot as an attribution, attr_ig telling the two kinds apart. Allocated by the first such call of
   // the context. ig_dev = baseline ids in device token order [Tmax] | ig [Tmax] (4-byte words); h_ig = the pinned staging of the baseline ids [Tmax], then ig [Tmax] |
-  // row statistics at the baseline [Rmax * 4] | at the real prompt [Rmax * 4] of the pending call. ig_on: forward() writes layer 0's input with embed_interp at
-  // ig_alpha instead of the embedding gather (set around the passes of tst_attribute_ig_async only).
+  // row statistics at the baseline [Rmax * 4] | at the real prompt [Rmax * 4] of the pending call.
   float* ig_dev = nullptr;
   float* h_ig = nullptr;
-  bool attr_ig = false, ig_on = false;
-  float ig_alpha = 1.0f;
+  bool attr_ig = false;
   float* d_loss = nullptr;
   int cur_T = 0, cur_S = 0, cur_R = 0, cur_maxlen = 0, cur_items = 0;
   double cur_sumsq_len = 0;   // sum over the batch's sequences of length^2 (attention work)
@@ -1052,9 +1050,17 @@ struct GenPass {
   int mode = 0, step = 0;
 };
 
+// what an attribution asks of its passes. backward: true = backward() is seeded by attr_seed instead of the loss gradient, forms the gradient of layer 0's input in
+// LoRA contexts too and no embedding gradient. interp: forward() writes layer 0's input with embed_interp at alpha, on the path from the baseline prompt's
+// embeddings (ig_dev) to the real ones (the passes of tst_attribute_ig_async), instead of the embedding gather.
+struct AttrPass {
+  bool backward = false, interp = false;
+  float alpha = 1.0f;
+};
+
 // forward through the decoder stack; stash=true keeps per-layer activations for the backward pass
 template <typename AT>
-int forward(CtxT<AT>* ctx, bool stash, GenPass gen = {}) {
+int forward(CtxT<AT>* ctx, bool stash, GenPass gen = {}, AttrPass ap = {}) {
   const int T = ctx->cur_T, d = ctx->d;
   hipStream_t st = ctx->stream;
   const float scale = 1.0f / sqrtf((float)ctx->dh);
@@ -1065,8 +1071,8 @@ int forward(CtxT<AT>* ctx, bool stash, GenPass gen = {}) {
   whatif_tick();   // (process-wide: the bench's contexts step in turn)
   CTX_RC(opt_need(ctx, 1));   // norm vectors / biases and the embedding side of a pending optimizer step
   // (an integrated-gradients pass enters the stack on the path from the baseline prompt's embeddings to the real ones; everything behind the embedding is unchanged)
-  if (ctx->ig_on) CTX_RC(embed_interp<AT>(st, ctx->d_ids, (const int*)ctx->ig_dev, ctx->d_pos, ctx->embed, ctx->gpt2 ? ctx->wpe : (const AT*)nullptr, L0.x_in, T, d, ctx->V,
-                                         ctx->npos, ctx->ig_alpha));
+  if (ap.interp) CTX_RC(embed_interp<AT>(st, ctx->d_ids, (const int*)ctx->ig_dev, ctx->d_pos, ctx->embed, ctx->gpt2 ? ctx->wpe : (const AT*)nullptr, L0.x_in, T, d, ctx->V,
+                                         ctx->npos, ap.alpha));
   else if (ctx->gpt2) CTX_RC(embed_pos_fwd<AT>(st, ctx->d_ids, ctx->d_pos, ctx->embed, ctx->wpe, L0.x_in, T, d, ctx->V, ctx->npos));
   else CTX_RC(embed_fwd<AT>(st, ctx->d_ids, ctx->embed, L0.x_in, T, d, ctx->V));
   for (int l = 0; l < ctx->L; ++l) {
@@ -1263,15 +1269,15 @@ int attr_seed_rows(CtxT<AT>* ctx) {
 // num_items: what the loss is normalised by (one slot); slot_items: per-slot counts of a stacked context (nullptr: every slot by its own labelled rows in this
 // batch). reduce_regions: a data-parallel full fine-tune's step -- the gradient regions are all-reduced on the communication stream as backward finishes them
 template <typename AT>
-int backward(CtxT<AT>* ctx, int num_items, const int32_t* slot_items = nullptr, bool reduce_regions = false) {
+int backward(CtxT<AT>* ctx, int num_items, const int32_t* slot_items = nullptr, bool reduce_regions = false, AttrPass ap = {}) {
   const int T = ctx->cur_T, d = ctx->d, R = ctx->cur_R;
   hipStream_t st = ctx->stream;
   const float scale = 1.0f / sqrtf((float)ctx->dh);
   const float inv_items = 1.0f / (float)num_items;
   const bool full = ctx->full;
-  // An attribution (attribute_async_impl) is this pass with two differences: the seed is d (sum_i log s(x_i)) / d logits instead of the loss gradient, and the
+  // An attribution (attr_forward_backward) is this pass with two differences: the seed is d (sum_i log s(x_i)) / d logits instead of the loss gradient, and the
   // gradient of layer 0's input is formed in LoRA contexts too. The weight- and adapter-gradient contractions stay in: the flat gradient is unspecified afterwards.
-  const bool attr = ctx->attr_pass;
+  const bool attr = ap.backward;
   CTX_RC(opt_join(ctx));     // (a no-op behind head_forward: backward overwrites the gradient a pending optimizer step reads)
   ctx->dw_side_open = false;
   ctx->ndw_open[0] = ctx->ndw_open[1] = false;
@@ -2626,9 +2632,17 @@ int ig_reserve(tst_ctx* ctx) {
   return TST_OK;
 }
 
-// The passes of an integrated-gradients call, behind the uploads of attribute_async_impl (which clears ig_on / attr_pass whatever this returns). Everything is
-// enqueued at once -- a forward + head pass at the baseline (alpha = 0) and one at the real prompt (alpha = 1) for the two log s, then n_steps times
-// embed_interp(alpha_k) -> forward -> head -> backward -> token_ig -- with no host wait in between; the caller records one event behind the result copies.
+// forward with the stash, head, and the backward pass of an attribution down to dX, the gradient of layer 0's input (backward joins its side streams)
+template <typename AT>
+int attr_forward_backward(CtxT<AT>* ctx, bool interp = false, float alpha = 1.0f) {
+  CTX_RC(forward(ctx, true, {}, AttrPass{false, interp, alpha}));
+  CTX_RC(head_forward(ctx, true));
+  return backward(ctx, ctx->cur_R, nullptr, false, AttrPass{true});
+}
+
+// The passes of an integrated-gradients call, behind the uploads of attribute_async_impl. Everything is enqueued at once -- a forward + head pass at the baseline
+// (alpha = 0) and one at the real prompt (alpha = 1) for the two log s, then n_steps times embed_interp(alpha_k) -> forward -> head -> backward -> token_ig -- with
+// no host wait in between; the caller records one event behind the result copies.
 template <typename AT>
 int ig_enqueue(CtxT<AT>* ctx, const int32_t* baseline_ids, int n_steps) {
   hipStream_t st = ctx->stream;
@@ -2640,27 +2654,18 @@ int ig_enqueue(CtxT<AT>* ctx, const int32_t* baseline_ids, int n_steps) {
   float* d_acc = ctx->ig_dev + Tmax;
   CTX_HIP(hipMemcpyAsync(d_bids, ctx->h_ig, (size_t)T * 4, hipMemcpyHostToDevice, st));
   float* h_res = ctx->h_ig + Tmax;
-  ctx->ig_on = true;
   for (int end = 0; end < 2; ++end) {   // log s at the baseline, then at the real prompt: attr_seed for the row statistics it leaves, no backward
-    ctx->ig_alpha = (float)end;
-    CTX_RC(forward(ctx, true));
+    CTX_RC(forward(ctx, true, {}, AttrPass{false, true, (float)end}));
     CTX_RC(head_forward(ctx, true));
     CTX_RC(attr_seed_rows(ctx));
     CTX_HIP(hipMemcpyAsync(h_res + Tmax + (size_t)end * 4 * Rmax, ctx->stats, (size_t)R * 16, hipMemcpyDeviceToHost, st));
   }
   const float w = 1.0f / (float)n_steps;
   for (int k = 1; k <= n_steps; ++k) {
-    ctx->ig_alpha = tsthost::ig_alpha(k, n_steps);
-    CTX_RC(forward(ctx, true));
-    CTX_RC(head_forward(ctx, true));
-    ctx->attr_pass = true;
-    const int brc = backward(ctx, R);
-    ctx->attr_pass = false;
-    CTX_RC(brc);
-    // (backward has joined its side streams: dX is the gradient at x_k; the step's term is taken against e - b from the table, not against x_k)
+    CTX_RC(attr_forward_backward(ctx, true, tsthost::ig_alpha(k, n_steps)));
+    // (dX is the gradient at x_k; the step's term is taken against e - b from the table, not against x_k)
     CTX_RC(token_ig<AT>(st, ctx->dX, ctx->embed, ctx->d_ids, d_bids, T, ctx->d, ctx->V, w, k == 1, d_acc));
   }
-  ctx->ig_on = false;
   CTX_HIP(hipMemcpyAsync(h_res, d_acc, (size_t)T * 4, hipMemcpyDeviceToHost, st));
   return TST_OK;
 }
@@ -2702,32 +2707,20 @@ int attribute_async_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* seq_k
   ctx->attr_cu_src.assign(b->cu_seqlens, b->cu_seqlens + S + 1);
   ctx->grad_stale = true;
   if (ig) {
-    ctx->attr_plan = std::move(plan);
-    const int rc = ig_enqueue(ctx, baseline_ids, n_steps);
-    ctx->ig_on = false;
-    ctx->attr_pass = false;
-    CTX_RC(rc);
-    CTX_HIP(hipEventRecord(ctx->attr_evt, st));
-    ctx->attr_ig = true;
-    ctx->attr_S = S;
-    return TST_OK;
+    CTX_RC(ig_enqueue(ctx, baseline_ids, n_steps));
+  } else {
+    CTX_RC(attr_forward_backward(ctx));
+    // (dX is the gradient of layer 0's stashed input, the embedding-layer output -- for GPT-2 wte + wpe)
+    float* gxi = ctx->attr_dev + head_words;
+    CTX_RC(token_attr<AT>(st, ctx->dX, ctx->layers[0].x_in, T, ctx->d, gxi, gxi + Tmax));
+    float* h_res = ctx->h_attr + head_words;
+    CTX_HIP(hipMemcpyAsync(h_res, gxi, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+    CTX_HIP(hipMemcpyAsync(h_res + Tmax, gxi + Tmax, (size_t)T * 4, hipMemcpyDeviceToHost, st));
+    CTX_HIP(hipMemcpyAsync(h_res + 2 * (size_t)Tmax, ctx->stats, (size_t)R * 16, hipMemcpyDeviceToHost, st));
   }
-  CTX_RC(forward(ctx, true));
-  CTX_RC(head_forward(ctx, true));
-  ctx->attr_pass = true;
-  const int brc = backward(ctx, R);
-  ctx->attr_pass = false;
-  CTX_RC(brc);
-  // (backward has joined its side streams: dX is the gradient of layer 0's stashed input, the embedding-layer output -- for GPT-2 wte + wpe)
-  float* gxi = ctx->attr_dev + head_words;
-  CTX_RC(token_attr<AT>(st, ctx->dX, ctx->layers[0].x_in, T, ctx->d, gxi, gxi + Tmax));
-  float* h_res = ctx->h_attr + head_words;
-  CTX_HIP(hipMemcpyAsync(h_res, gxi, (size_t)T * 4, hipMemcpyDeviceToHost, st));
-  CTX_HIP(hipMemcpyAsync(h_res + Tmax, gxi + Tmax, (size_t)T * 4, hipMemcpyDeviceToHost, st));
-  CTX_HIP(hipMemcpyAsync(h_res + 2 * (size_t)Tmax, ctx->stats, (size_t)R * 16, hipMemcpyDeviceToHost, st));
   CTX_HIP(hipEventRecord(ctx->attr_evt, st));
   ctx->attr_plan = std::move(plan);
-  ctx->attr_ig = false;
+  ctx->attr_ig = ig;
   ctx->attr_S = S;
   return TST_OK;
 }
@@ -3243,12 +3236,20 @@ int tst_score_async(tst_ctx* ctx, const tst_batch* b, const int32_t* option_ids,
   return typed(ctx, [&](auto* c) { return score_async_impl(c, b, option_ids, n_opt); });
 }
 
+// the opening of every *_fetch: nothing pending (count < 0) -> TST_ESTATE with `none`; else wait for the event recorded behind the pass's result copies (work
+// enqueued after the pass, such as the next train steps, keeps running), hand the count out and clear it
+int take_pending(tst_ctx* ctx, int& pending, hipEvent_t evt, const char* none, int& n) {
+  if (pending < 0) return fail(ctx, TST_ESTATE, none);
+  CTX_RC(ctx_event_sync(ctx, evt));
+  n = pending;
+  pending = -1;
+  return TST_OK;
+}
+
 int tst_score_fetch(tst_ctx* ctx, float* logp_out, int32_t* correct_out, float* opt_logit_out, int32_t* row_seq_out, int32_t* n_rows_out) {
+  int R;
   if (!ctx) return TST_EINVAL;
-  if (ctx->score_R < 0) return fail(ctx, TST_ESTATE, "tst_score_fetch without a pending tst_score_async");
-  CTX_RC(ctx_event_sync(ctx, ctx->score_evt));   // work enqueued after the scoring pass (the next train steps) keeps running
-  const int R = ctx->score_R;
-  ctx->score_R = -1;
+  CTX_RC(take_pending(ctx, ctx->score_R, ctx->score_evt, "tst_score_fetch without a pending tst_score_async", R));
   if (n_rows_out) *n_rows_out = R;
   const float* st = ctx->h_score;
   for (int r = 0; r < R; ++r) {
@@ -3275,12 +3276,10 @@ int tst_attribute_async(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_kin
 }
 
 int tst_attribute_fetch(tst_ctx* ctx, float* gxi_out, float* gnorm_out, float* logs_out) {
+  int S;
   if (!ctx) return TST_EINVAL;
-  if (ctx->attr_S < 0) return fail(ctx, TST_ESTATE, "tst_attribute_fetch without a pending tst_attribute_async");
-  if (ctx->attr_ig) return fail(ctx, TST_ESTATE, "the pending attribution is a tst_attribute_ig_async: fetch it with tst_attribute_ig_fetch");
-  CTX_RC(ctx_event_sync(ctx, ctx->attr_evt));   // work enqueued after the attribution keeps running
-  const int S = ctx->attr_S;
-  ctx->attr_S = -1;
+  if (ctx->attr_S >= 0 && ctx->attr_ig) return fail(ctx, TST_ESTATE, "the pending attribution is a tst_attribute_ig_async: fetch it with tst_attribute_ig_fetch");
+  CTX_RC(take_pending(ctx, ctx->attr_S, ctx->attr_evt, "tst_attribute_fetch without a pending tst_attribute_async", S));
   const float* h_res = ctx->h_attr + 2 * (size_t)ctx->Rmax + tsthost::kAttrMaxOpt;
   // the caller's token order: a token trim_last_token kept off the device gets 0 (nothing reads it under the causal mask: its gradient is exactly 0)
   if (gxi_out && tsthost::untrim_tokens(h_res, ctx->attr_cu_dev.data(), ctx->attr_cu_src.data(), S, gxi_out) != TST_OK) return fail(ctx, TST_EINVAL, "internal: un-trim map");
@@ -3304,12 +3303,10 @@ int tst_attribute_ig_async(tst_ctx* ctx, const tst_batch* b, const int32_t* seq_
 }
 
 int tst_attribute_ig_fetch(tst_ctx* ctx, float* ig_out, float* logs_out, float* logs_base_out) {
+  int S;
   if (!ctx) return TST_EINVAL;
-  if (ctx->attr_S < 0) return fail(ctx, TST_ESTATE, "tst_attribute_ig_fetch without a pending tst_attribute_ig_async");
-  if (!ctx->attr_ig) return fail(ctx, TST_ESTATE, "the pending attribution is a tst_attribute_async: fetch it with tst_attribute_fetch");
-  CTX_RC(ctx_event_sync(ctx, ctx->attr_evt));   // work enqueued after the attribution keeps running
-  const int S = ctx->attr_S;
-  ctx->attr_S = -1;
+  if (ctx->attr_S >= 0 && !ctx->attr_ig) return fail(ctx, TST_ESTATE, "the pending attribution is a tst_attribute_async: fetch it with tst_attribute_fetch");
+  CTX_RC(take_pending(ctx, ctx->attr_S, ctx->attr_evt, "tst_attribute_ig_fetch without a pending tst_attribute_ig_async", S));
   ctx->attr_ig = false;
   const float* h_res = ctx->h_ig + ctx->Tmax;
   if (ig_out && tsthost::untrim_tokens(h_res, ctx->attr_cu_dev.data(), ctx->attr_cu_src.data(), S, ig_out) != TST_OK) return fail(ctx, TST_EINVAL, "internal: un-trim map");
@@ -3332,11 +3329,10 @@ int tst_generate_async(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens,
 }
 
 int tst_generate_fetch(tst_ctx* ctx, int32_t* tokens_out, float* logp_out, int32_t* n_new_out) {
+  int S;
   if (!ctx) return TST_EINVAL;
-  if (ctx->gen_S < 0) return fail(ctx, TST_ESTATE, "tst_generate_fetch without a pending tst_generate_async");
-  CTX_RC(ctx_event_sync(ctx, ctx->gen_evt));   // work enqueued after the generation keeps running
-  const int S = ctx->gen_S, n = ctx->gen_new;
-  ctx->gen_S = -1;
+  CTX_RC(take_pending(ctx, ctx->gen_S, ctx->gen_evt, "tst_generate_fetch without a pending tst_generate_async", S));
+  const int n = ctx->gen_new;
   const int32_t* h_tok = (const int32_t*)(ctx->h_gen + ctx->gen_dev_bytes / 4);
   const float* h_lp = (const float*)h_tok + (size_t)ctx->Smax * ctx->gen_cap_new;
   std::vector<int32_t> tok(h_tok, h_tok + (size_t)S * n);

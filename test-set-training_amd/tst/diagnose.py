@@ -23,10 +23,8 @@ import time
 import numpy as np
 
 from . import kfold
-from .trainer import (attribute_heldout, attribute_heldout_concurrent, attribute_heldout_stacked)
-from .trainer import (attribute_ig_heldout, attribute_ig_heldout_concurrent, attribute_ig_heldout_stacked)
-from .trainer import (TrainArgs, fine_tune, fine_tune_concurrent, fine_tune_dp, fine_tune_stacked, generate_heldout, generate_heldout_concurrent,
-                      generate_heldout_stacked, score_heldout, score_heldout_concurrent, score_heldout_stacked)
+from .trainer import (ATTRIBUTE, GENERATE, IG, SCORE, TrainArgs, fine_tune, fine_tune_concurrent, fine_tune_dp, fine_tune_stacked, run_heldout,
+                      run_heldout_concurrent, run_heldout_stacked)
 
 GEN_ARGS = ("generate", "max_new_tokens", "eos_ids")   # TrainArgs fields that enter the run fingerprint only when generation is on
 ATTR_ARGS = ("attribute", "attribute_top")             # TrainArgs settings that enter it only when attribution is on
@@ -101,9 +99,19 @@ def train_health(recs):
                 grad_norm_min=float(gn.min()), grad_norm_max=float(gn.max()))
 
 
-def fold_records(held, f, rnd, s, pred, correct, gen=None, decode=None, attr=None, attr_top=5, ig=None):
-    """the records of one scored held-out fold; gen = [(gen ids, gen_correct)] per sample when generation is on, decode = ids -> text;
-    attr = tst.score.token_attribution's dict per sample when attribution is on; ig = tst.score.token_ig's when integrated gradients are"""
+def heldout_passes(layout, ctxs, helds, args: TrainArgs):
+    """score, then every enabled extra pass (generate, attribute, ig: in this order) over the held-out folds. layout: "one" (ctxs is one context, helds one fold),
+    "concurrent" (a context per fold) or "stacked". Per fold: ((s, pred, correct), extras), extras = {"gen" / "attr" / "ig": per-sample results} of what ran."""
+    run = dict(one=lambda p, c, sets, a: [run_heldout(p, c, sets[0], a)], concurrent=run_heldout_concurrent, stacked=run_heldout_stacked)[layout]
+    scored = run(SCORE, ctxs, helds, args)
+    enabled = (("gen", GENERATE, args.generate), ("attr", ATTRIBUTE, args.attribute), ("ig", IG, args.attribute_ig > 0))
+    ran = {key: run(p, ctxs, helds, args) for key, p, on in enabled if on}
+    return [(sc, {key: got[i] for key, got in ran.items()}) for i, sc in enumerate(scored)]
+
+
+def fold_records(held, f, rnd, s, pred, correct, decode=None, attr_top=5, *, gen=None, attr=None, ig=None):
+    """the records of one scored held-out fold; decode = ids -> text; the extras (heldout_passes' mapping, as keywords): gen = [(gen ids, gen_correct)] per sample
+    when generation is on, attr = tst.score.token_attribution's dict when attribution is on, ig = tst.score.token_ig's when integrated gradients are"""
     records = [dict(id=int(x.sid), fold=int(f), round=int(rnd), s=float(si), pred=int(pi), correct=int(ci), kind=x.kind)
                for x, si, pi, ci in zip(held, s, pred, correct)]
     if gen is not None:
@@ -139,12 +147,9 @@ def run_fold(ctx, samples, assign, f, args: TrainArgs, rnd=0, out_dir=None, log=
     recs_train = fine_tune(ctx, [samples[i] for i in train_idx], args, fold_seed=f, log=flog)
     t1 = time.perf_counter()
     held = [samples[i] for i in held_idx]
-    s, pred, correct = score_heldout(ctx, held, args)
-    gen = generate_heldout(ctx, held, args) if args.generate else None
-    attr = attribute_heldout(ctx, held, args) if args.attribute else None
-    ig = attribute_ig_heldout(ctx, held, args) if args.attribute_ig > 0 else None
+    [((s, pred, correct), extras)] = heldout_passes("one", ctx, [held], args)
     t2 = time.perf_counter()
-    records = fold_records(held, f, rnd, s, pred, correct, gen, decode, attr, args.attribute_top, ig)
+    records = fold_records(held, f, rnd, s, pred, correct, decode, args.attribute_top, **extras)
     if out_dir:
         _write_shard(out_dir, rnd, f, records)
     stats = dict(fold=f, n_train=len(train_idx), n_heldout=len(held_idx), train_s=t1 - t0, score_s=t2 - t1,
@@ -175,17 +180,13 @@ def run_fold_group(ctxs, samples, assign, fold_ids, args: TrainArgs, rnd=0, out_
     logs = (fine_tune_stacked if stacked else fine_tune_concurrent)(ctxs, trains, args, list(fold_ids), flog)
     t1 = time.perf_counter()
     helds = [[samples[i] for i in he] for _, he in idx]
-    scored = (score_heldout_stacked if stacked else score_heldout_concurrent)(ctxs, helds, args)
-    gens = (generate_heldout_stacked if stacked else generate_heldout_concurrent)(ctxs, helds, args) if args.generate else [None] * len(helds)
-    attrs = (attribute_heldout_stacked if stacked else attribute_heldout_concurrent)(ctxs, helds, args) if args.attribute else [None] * len(helds)
-    igs = (attribute_ig_heldout_stacked if stacked else attribute_ig_heldout_concurrent)(ctxs, helds, args) if args.attribute_ig > 0 else [None] * len(helds)
+    passed = heldout_passes("stacked" if stacked else "concurrent", ctxs, helds, args)
     t2 = time.perf_counter()
     if os.environ.get("TST_PHASE_LOG"):
-        import sys
         print(f"[phase] fold group {list(fold_ids)}: train {t1 - t0:.3f} s, score {t2 - t1:.3f} s", file=sys.stderr)
     all_records, stats = [], []
-    for f, (tr, he), held, (s, pred, correct), gen, attr, ig, lg in zip(fold_ids, idx, helds, scored, gens, attrs, igs, logs):
-        records = fold_records(held, f, rnd, s, pred, correct, gen, decode, attr, args.attribute_top, ig)
+    for f, (tr, he), held, ((s, pred, correct), extras), lg in zip(fold_ids, idx, helds, passed, logs):
+        records = fold_records(held, f, rnd, s, pred, correct, decode, args.attribute_top, **extras)
         if out_dir:
             _write_shard(out_dir, rnd, f, records)
         all_records += records
@@ -254,10 +255,9 @@ def diagnose_dp(ctx, samples, k, args: TrainArgs, rank, world, dp, rnd=0, out_di
         if dp_rank != 0:
             continue   # the replicas are identical: one of them scores
         held = [samples[i] for i in he]
-        s, pred, correct = score_heldout(ctx, held, args)
-        gen = generate_heldout(ctx, held, args) if args.generate else None
+        [((s, pred, correct), extras)] = heldout_passes("one", ctx, [held], args)
         t2 = time.perf_counter()
-        recs = fold_records(held, f, rnd, s, pred, correct, gen, decode)
+        recs = fold_records(held, f, rnd, s, pred, correct, decode, **extras)
         if out_dir:
             _write_shard(out_dir, rnd, f, recs)
         records += recs
@@ -304,11 +304,10 @@ def diagnose_dp_stacked(ctxs, samples, k, args: TrainArgs, rank, world, rnd=0, o
         logs = fine_tune_stacked(group, [[samples[i] for i in tr] for tr, _ in idx], args, list(fold_ids), flog, dp=(rank, world))
         t1 = time.perf_counter()
         helds = [[samples[i] for i in he][rank::world] for _, he in idx]      # this rank's part of every held-out fold
-        scored = score_heldout_stacked(group, helds, args)
-        gens = generate_heldout_stacked(group, helds, args) if args.generate else [None] * len(helds)
+        passed = heldout_passes("stacked", group, helds, args)
         t2 = time.perf_counter()
-        for f, (tr, he), held, (s, pred, correct), gen, lg in zip(fold_ids, idx, helds, scored, gens, logs):
-            recs = fold_records(held, f, rnd, s, pred, correct, gen, decode)
+        for f, (tr, he), held, ((s, pred, correct), extras), lg in zip(fold_ids, idx, helds, passed, logs):
+            recs = fold_records(held, f, rnd, s, pred, correct, decode, **extras)
             if out_dir:
                 parts = gather(recs)
                 if rank == 0:

@@ -501,6 +501,15 @@ def _i32(a):
     return a, a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _options(b, option_ids, seq_kind=None):
+    """(option-id array, its length, seq_kind array or None) of a scoring / attribution call on batch b (no options: one zero, length 0)"""
+    opt_a, _ = _i32(np.asarray(option_ids, np.int32) if len(option_ids) else np.zeros(1, np.int32))
+    kind_a = None if seq_kind is None else np.ascontiguousarray(seq_kind, np.int32)
+    if kind_a is not None and len(kind_a) != b.n_seqs:
+        raise TstError("seq_kind needs one entry per sequence")
+    return opt_a, len(option_ids), kind_a
+
+
 def to_bf16_bits(x):
     u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
     r = ((u >> np.uint32(16)) & np.uint32(1)) + np.uint32(0x7FFF)
@@ -908,8 +917,7 @@ class Context:
     def score_rows_async(self, ids, labels, cu, option_ids=(), seq_slot=None):
         """enqueue a held-out scoring pass; results come from score_rows_fetch()."""
         b, keep = self._batch(ids, labels, cu, seq_slot)
-        n_opt = len(option_ids)
-        opt_a, _ = _i32(np.asarray(option_ids, np.int32) if n_opt else np.zeros(1, np.int32))
+        opt_a, n_opt, _ = _options(b, option_ids)
         self._check(self.lib.tst_score_async(self.h, C.byref(b), _ptr(opt_a), n_opt), "tst_score_async")
         self._pending_nopt = n_opt
 
@@ -953,11 +961,7 @@ class Context:
         """enqueue the input-gradient attribution of log s(x) for the packed batch; seq_kind[i] = 0 (open form: mean log-probability of the labelled tokens) or
         1 (option form: the one labelled token against option_ids); None = all open. Results come from attribute_fetch()."""
         b, keep = self._batch(ids, labels, cu, seq_slot)
-        n_opt = len(option_ids)
-        opt_a, _ = _i32(np.asarray(option_ids, np.int32) if n_opt else np.zeros(1, np.int32))
-        kind_a = None if seq_kind is None else np.ascontiguousarray(seq_kind, np.int32)
-        if kind_a is not None and len(kind_a) != len(keep[2]) - 1:
-            raise TstError("seq_kind needs one entry per sequence")
+        opt_a, n_opt, kind_a = _options(b, option_ids, seq_kind)
         self._check(self.lib.tst_attribute_async(self.h, C.byref(b), None if kind_a is None else _ptr(kind_a), _ptr(opt_a), n_opt), "tst_attribute_async")
         self._pending_attr = (len(keep[0]), len(keep[2]) - 1)
 
@@ -978,11 +982,7 @@ class Context:
         """enqueue the integrated gradients of log s(x) from the baseline prompt baseline_ids (host ids, one per token; a token whose baseline is its own id is not
         interpolated) to the packed batch, n_steps midpoint steps. seq_kind / option_ids as for attribute_async. Results come from attribute_ig_fetch()."""
         b, keep = self._batch(ids, labels, cu, seq_slot)
-        n_opt = len(option_ids)
-        opt_a, _ = _i32(np.asarray(option_ids, np.int32) if n_opt else np.zeros(1, np.int32))
-        kind_a = None if seq_kind is None else np.ascontiguousarray(seq_kind, np.int32)
-        if kind_a is not None and len(kind_a) != len(keep[2]) - 1:
-            raise TstError("seq_kind needs one entry per sequence")
+        opt_a, n_opt, kind_a = _options(b, option_ids, seq_kind)
         base_a = None if baseline_ids is None else np.ascontiguousarray(baseline_ids, np.int32)
         if base_a is not None and len(base_a) != b.n_tokens:
             raise TstError("baseline_ids needs one entry per token")

@@ -7,6 +7,7 @@ batch of 16 is the value BASELINE.md fixes for the metric."""
 import os
 import time
 from dataclasses import InitVar, dataclass
+from typing import Callable, NamedTuple
 
 import numpy as np
 
@@ -172,48 +173,6 @@ def fine_tune_concurrent(ctxs, sample_sets, args: TrainArgs, fold_seeds, log=Non
     return records
 
 
-def score_heldout_concurrent(ctxs, sample_sets, args: TrainArgs):
-    """held-out scoring of several resident folds: batch b of every fold is enqueued before batch b-1's results are read."""
-    bs = args.per_device_eval_batch_size
-    outs = [([], [], []) for _ in ctxs]
-    pending = [None] * len(ctxs)
-
-    def fetch(j):
-        if pending[j] is not None:
-            logp, corr, optl, rseq = ctxs[j].score_rows_fetch()
-            s, p, c = S.bias_scores(pending[j], logp, corr, optl, rseq)
-            outs[j][0].append(s); outs[j][1].append(p); outs[j][2].append(c)
-            pending[j] = None
-
-    nb = max((len(smp) + bs - 1) // bs for smp in sample_sets) if sample_sets else 0
-    for b in range(nb):
-        for j, (c, smp) in enumerate(zip(ctxs, sample_sets)):
-            fetch(j)
-            batch = smp[b * bs:(b + 1) * bs]
-            if batch:
-                ids, labels, cu = D.collate(batch)
-                c.score_rows_async(ids, labels, cu, args.option_ids)
-                pending[j] = batch
-    for j in range(len(ctxs)):
-        fetch(j)
-    empty_f, empty_i = np.zeros(0, np.float32), np.zeros(0, np.int32)
-    return [(np.concatenate(o[0]) if o[0] else empty_f, np.concatenate(o[1]) if o[1] else empty_i, np.concatenate(o[2]) if o[2] else empty_i) for o in outs]
-
-
-def score_heldout(ctx, samples, args: TrainArgs):
-    """forward-only pass over the held-out fold; returns s(x), pred, correct per sample (batch order = input order)."""
-    bs = args.per_device_eval_batch_size
-    s_all, p_all, c_all = [], [], []
-    for b in range(0, len(samples), bs):
-        batch = samples[b:b + bs]
-        ids, labels, cu = D.collate(batch)
-        logp, corr, optl, rseq = ctx.score_rows(ids, labels, cu, args.option_ids)
-        s, p, c = S.bias_scores(batch, logp, corr, optl, rseq)
-        s_all.append(s); p_all.append(p); c_all.append(c)
-    return np.concatenate(s_all), np.concatenate(p_all), np.concatenate(c_all)
-
-
-# ---------------------------------------------------------------------------------------------- greedy answers of the held-out fold
 def collate_prompts(samples):
     """packed prompts (ids[:n_prompt] of every sample): ids, cu_seqlens"""
     ids = np.concatenate([s.ids[:s.n_prompt] for s in samples]).astype(np.int32)
@@ -221,182 +180,143 @@ def collate_prompts(samples):
     return ids, cu
 
 
-def generate_heldout(ctx, samples, args: TrainArgs):
-    """greedy continuation of every held-out prompt (Context.generate, batches of per_device_eval_batch_size); returns [(gen ids, gen_correct)]
-    per sample in input order (tst.score.generated_answers)."""
+# ---------------------------------------------------------------------------------------------- passes over the held-out fold
+class HeldoutPass(NamedTuple):
+    """one kind of pass over held-out samples, for the three drivers below"""
+    enqueue: Callable   # (ctx, samples, args, *seq_slot): collate the flat sample list and enqueue it on the context (seq_slot: stacked contexts only)
+    fetch: Callable     # (ctx, samples, args) -> one result per sample of the batch pending on the context
+    join: Callable      # (per-sample results of a fold, in input order) -> what the fold's caller gets
+
+
+def _score_enqueue(ctx, batch, args, *seq_slot):
+    ids, labels, cu = D.collate(batch)
+    ctx.score_rows_async(ids, labels, cu, args.option_ids, *seq_slot)
+
+
+def _score_join(rows):
+    s, pred, correct = zip(*rows) if rows else ((), (), ())
+    return np.array(s, np.float32), np.array(pred, np.int32), np.array(correct, np.int32)
+
+
+def _generate_enqueue(ctx, batch, args, *seq_slot):
+    ids, cu = collate_prompts(batch)
+    ctx.generate_async(ids, cu, args.max_new_tokens, args.eos_ids, *seq_slot)
+
+
+def _generate_fetch(ctx, batch, args):
+    tok, _, n_new = ctx.generate_fetch()
+    return S.generated_answers(batch, tok, n_new, args.eos_ids)
+
+
+def _attribute_enqueue(ctx, batch, args, *seq_slot):
+    ids, labels, cu = D.collate(batch)
+    ctx.attribute_async(ids, labels, cu, S.attribution_kinds(batch), args.option_ids, *seq_slot)   # MCA and open samples in one batch
+
+
+def _ig_enqueue(ctx, batch, args, *seq_slot):
+    ids, labels, cu = D.collate(batch)
+    ctx.attribute_ig_async(ids, labels, cu, S.ig_baseline_ids(batch, args.attribute_baseline_id), args.attribute_ig, S.attribution_kinds(batch), args.option_ids,
+                           *seq_slot)
+
+
+# s(x), pred, correct per sample (tst.score.bias_scores): a fold gets three arrays
+SCORE = HeldoutPass(_score_enqueue, lambda ctx, batch, args: list(zip(*S.bias_scores(batch, *ctx.score_rows_fetch()))), _score_join)
+# greedy continuation of every prompt by args.max_new_tokens tokens: [(gen ids, gen_correct)] (tst.score.generated_answers)
+GENERATE = HeldoutPass(_generate_enqueue, _generate_fetch, list)
+# input-gradient attribution of log s(x): tst.score.token_attribution's dict per sample. About one training forward + backward per batch.
+ATTRIBUTE = HeldoutPass(_attribute_enqueue, lambda ctx, batch, args: S.token_attribution(batch, *ctx.attribute_fetch()), list)
+# integrated gradients of log s(x), args.attribute_ig steps from a prompt of args.attribute_baseline_id: tst.score.token_ig's dict per sample.
+# args.attribute_ig forward + backward passes and two forward passes per batch (measured: DESIGN.md section 14)
+IG = HeldoutPass(_ig_enqueue, lambda ctx, batch, args: S.token_ig(batch, *ctx.attribute_ig_fetch()), list)
+
+
+def run_heldout(p: HeldoutPass, ctx, samples, args: TrainArgs):
+    """pass p over one context's held-out fold in batches of per_device_eval_batch_size; results in input order"""
+    if p is SCORE and not hasattr(ctx, "score_rows_async"):
+        ctx = _SyncScorer(ctx)
     bs = args.per_device_eval_batch_size
     out = []
     for b in range(0, len(samples), bs):
-        batch = samples[b:b + bs]
-        ids, cu = collate_prompts(batch)
-        tok, _, n_new = ctx.generate(ids, cu, args.max_new_tokens, args.eos_ids)
-        out += S.generated_answers(batch, tok, n_new, args.eos_ids)
-    return out
+        p.enqueue(ctx, samples[b:b + bs], args)
+        out += p.fetch(ctx, samples[b:b + bs], args)
+    return p.join(out)
 
 
-def generate_heldout_concurrent(ctxs, sample_sets, args: TrainArgs):
-    """generate_heldout for several resident folds: batch b of every fold is enqueued before batch b-1's results are read."""
-    bs = args.per_device_eval_batch_size
-    outs = [[] for _ in ctxs]
-    pending = [None] * len(ctxs)
-
-    def fetch(j):
-        if pending[j] is not None:
-            tok, _, n_new = ctxs[j].generate_fetch()
-            outs[j] += S.generated_answers(pending[j], tok, n_new, args.eos_ids)
-            pending[j] = None
-
-    nb = max((len(smp) + bs - 1) // bs for smp in sample_sets) if sample_sets else 0
-    for b in range(nb):
-        for j, (c, smp) in enumerate(zip(ctxs, sample_sets)):
-            fetch(j)
-            batch = smp[b * bs:(b + 1) * bs]
-            if batch:
-                ids, cu = collate_prompts(batch)
-                c.generate_async(ids, cu, args.max_new_tokens, args.eos_ids)
-                pending[j] = batch
-    for j in range(len(ctxs)):
-        fetch(j)
-    return outs
+def run_heldout_concurrent(p: HeldoutPass, ctxs, sample_sets, args: TrainArgs):
+    """pass p over several resident folds, one per context: batch b of every fold is enqueued before batch b-1's results are read."""
+    return _run_heldout_groups(p, ctxs, [[(i, None)] for i in range(len(sample_sets))], sample_sets, args)
 
 
-def generate_heldout_stacked(ctxs, sample_sets, args: TrainArgs):
-    """generate_heldout on stacked contexts: batch b of all folds of a context is one generation, every sequence under its own slot's adapters;
-    returns [(gen ids, gen_correct)] per fold, in the order of sample_sets."""
+def run_heldout_stacked(p: HeldoutPass, ctxs, sample_sets, args: TrainArgs):
+    """pass p on stacked contexts: batch b of all folds of a context is one pass, every sequence under its own slot's adapters (place_folds decides the
+    slots, the batch is concatenated in slot order); returns the joined results per fold, in the order of sample_sets."""
     where = place_folds(len(sample_sets), ctxs)
+    return _run_heldout_groups(p, ctxs, [[(i, sl) for i, (jj, sl) in enumerate(where) if jj == j] for j in range(len(ctxs))], sample_sets, args)
+
+
+def _run_heldout_groups(p, ctxs, mine, sample_sets, args):
+    """mine[j]: the (fold position, slot) pairs context j runs; slot None = a plain context, which gets no seq_slot argument. On a context the previous batch
+    is fetched right before the next one is enqueued; batch b goes to every context before batch b + 1 goes to any."""
     bs = args.per_device_eval_batch_size
     outs = [[] for _ in sample_sets]
     pending = [None] * len(ctxs)
-    mine = [[(sl, i) for i, (jj, sl) in enumerate(where) if jj == j] for j in range(len(ctxs))]
 
     def fetch(j):
         if pending[j] is not None:
             parts = pending[j]   # [(fold position, samples)]
-            tok, _, n_new = ctxs[j].generate_fetch()
-            got = S.generated_answers([x for _, b in parts for x in b], tok, n_new, args.eos_ids)
+            got = p.fetch(ctxs[j], [x for _, xs in parts for x in xs], args)
             o = 0
-            for i, b in parts:
-                outs[i] += got[o:o + len(b)]
-                o += len(b)
+            for i, xs in parts:
+                outs[i] += got[o:o + len(xs)]
+                o += len(xs)
             pending[j] = None
 
     nb = max((len(smp) + bs - 1) // bs for smp in sample_sets) if sample_sets else 0
     for b in range(nb):
-        for j, c in enumerate(ctxs):
+        for j, (c, folds) in enumerate(zip(ctxs, mine)):
             fetch(j)
-            parts = [(sl, i, sample_sets[i][b * bs:(b + 1) * bs]) for sl, i in mine[j]]
-            parts = [(sl, i, x) for sl, i, x in parts if x]
+            parts = [(sl, i, sample_sets[i][b * bs:(b + 1) * bs]) for i, sl in folds]
+            parts = [(sl, i, xs) for sl, i, xs in parts if xs]
             if parts:
-                ids, cu = collate_prompts([x for _, _, xs in parts for x in xs])
-                seq_slot = np.concatenate([np.full(len(xs), sl, np.int32) for sl, _, xs in parts])
-                c.generate_async(ids, cu, args.max_new_tokens, args.eos_ids, seq_slot)
+                seq_slot = [] if parts[0][0] is None else [np.concatenate([np.full(len(xs), sl, np.int32) for sl, _, xs in parts])]
+                p.enqueue(c, [x for _, _, xs in parts for x in xs], args, *seq_slot)
                 pending[j] = [(i, xs) for _, i, xs in parts]
     for j in range(len(ctxs)):
         fetch(j)
-    return outs
+    return [p.join(o) for o in outs]
 
 
-# ---------------------------------------------------------------------------------------------- token attribution of the held-out fold
-def _attribute_async(ctx, batch, args: TrainArgs, seq_slot=None):
-    ids, labels, cu = D.collate(batch)
-    ctx.attribute_async(ids, labels, cu, S.attribution_kinds(batch), args.option_ids, seq_slot)   # MCA and open samples in one batch
+class _SyncScorer:
+    """score_rows_async / score_rows_fetch over a model that only has the synchronous score_rows (the oracle models)"""
+
+    def __init__(self, model):
+        self.model = model
+
+    def score_rows_async(self, *batch):
+        self.rows = self.model.score_rows(*batch)
+
+    def score_rows_fetch(self):
+        return self.rows
 
 
-def _ig_async(ctx, batch, args: TrainArgs, seq_slot=None):
-    ids, labels, cu = D.collate(batch)
-    ctx.attribute_ig_async(ids, labels, cu, S.ig_baseline_ids(batch, args.attribute_baseline_id), args.attribute_ig, S.attribution_kinds(batch), args.option_ids,
-                           seq_slot)
+def score_heldout(ctx, samples, args: TrainArgs):
+    """forward-only pass over the held-out fold; returns s(x), pred, correct per sample (batch order = input order)."""
+    return run_heldout(SCORE, ctx, samples, args)
 
 
-# what the three held-out drivers below run: (enqueue on a context, turn a fetched batch into per-sample dicts)
-_ATTR = (_attribute_async, lambda ctx, batch: S.token_attribution(batch, *ctx.attribute_fetch()))
-_IG = (_ig_async, lambda ctx, batch: S.token_ig(batch, *ctx.attribute_ig_fetch()))
+def generate_heldout(ctx, samples, args: TrainArgs):
+    """greedy continuation of every held-out prompt; returns [(gen ids, gen_correct)] per sample in input order."""
+    return run_heldout(GENERATE, ctx, samples, args)
+
+
+def attribute_heldout(ctx, samples, args: TrainArgs):
+    """input-gradient attribution of log s(x) for every held-out sample; returns tst.score.token_attribution's dict per sample in input order."""
+    return run_heldout(ATTRIBUTE, ctx, samples, args)
 
 
 def attribute_ig_heldout(ctx, samples, args: TrainArgs):
-    """integrated gradients of log s(x) for every held-out sample (Context.attribute_ig: args.attribute_ig steps from a prompt of args.attribute_baseline_id);
-    returns tst.score.token_ig's dict per sample in input order. args.attribute_ig forward + backward passes and two forward passes per batch (measured: DESIGN.md section 14)."""
-    return attribute_heldout(ctx, samples, args, _IG)
-
-
-def attribute_ig_heldout_concurrent(ctxs, sample_sets, args: TrainArgs):
-    """attribute_ig_heldout for several resident folds (as attribute_heldout_concurrent)"""
-    return attribute_heldout_concurrent(ctxs, sample_sets, args, _IG)
-
-
-def attribute_ig_heldout_stacked(ctxs, sample_sets, args: TrainArgs):
-    """attribute_ig_heldout on stacked contexts (as attribute_heldout_stacked)"""
-    return attribute_heldout_stacked(ctxs, sample_sets, args, _IG)
-
-
-def attribute_heldout(ctx, samples, args: TrainArgs, how=_ATTR):
-    """input-gradient attribution of log s(x) for every held-out sample (Context.attribute, batches of per_device_eval_batch_size); returns
-    tst.score.token_attribution's dict per sample in input order. About one training forward + backward per batch."""
-    bs = args.per_device_eval_batch_size
-    out = []
-    for b in range(0, len(samples), bs):
-        batch = samples[b:b + bs]
-        how[0](ctx, batch, args)
-        out += how[1](ctx, batch)
-    return out
-
-
-def attribute_heldout_concurrent(ctxs, sample_sets, args: TrainArgs, how=_ATTR):
-    """attribute_heldout for several resident folds: batch b of every fold is enqueued before batch b-1's results are read."""
-    bs = args.per_device_eval_batch_size
-    outs = [[] for _ in ctxs]
-    pending = [None] * len(ctxs)
-
-    def fetch(j):
-        if pending[j] is not None:
-            outs[j] += how[1](ctxs[j], pending[j])
-            pending[j] = None
-
-    nb = max((len(smp) + bs - 1) // bs for smp in sample_sets) if sample_sets else 0
-    for b in range(nb):
-        for j, (c, smp) in enumerate(zip(ctxs, sample_sets)):
-            fetch(j)
-            batch = smp[b * bs:(b + 1) * bs]
-            if batch:
-                how[0](c, batch, args)
-                pending[j] = batch
-    for j in range(len(ctxs)):
-        fetch(j)
-    return outs
-
-
-def attribute_heldout_stacked(ctxs, sample_sets, args: TrainArgs, how=_ATTR):
-    """attribute_heldout on stacked contexts: batch b of all folds of a context is one attribution, every sequence under its own slot's adapters;
-    returns the per-sample dicts per fold, in the order of sample_sets."""
-    where = place_folds(len(sample_sets), ctxs)
-    bs = args.per_device_eval_batch_size
-    outs = [[] for _ in sample_sets]
-    pending = [None] * len(ctxs)
-    mine = [[(sl, i) for i, (jj, sl) in enumerate(where) if jj == j] for j in range(len(ctxs))]
-
-    def fetch(j):
-        if pending[j] is not None:
-            parts = pending[j]   # [(fold position, samples)]
-            got = how[1](ctxs[j], [x for _, b in parts for x in b])
-            o = 0
-            for i, b in parts:
-                outs[i] += got[o:o + len(b)]
-                o += len(b)
-            pending[j] = None
-
-    nb = max((len(smp) + bs - 1) // bs for smp in sample_sets) if sample_sets else 0
-    for b in range(nb):
-        for j, c in enumerate(ctxs):
-            fetch(j)
-            parts = [(sl, i, sample_sets[i][b * bs:(b + 1) * bs]) for sl, i in mine[j]]
-            parts = [(sl, i, x) for sl, i, x in parts if x]
-            if parts:
-                seq_slot = np.concatenate([np.full(len(xs), sl, np.int32) for sl, _, xs in parts])
-                how[0](c, [x for _, _, xs in parts for x in xs], args, seq_slot)
-                pending[j] = [(i, xs) for _, i, xs in parts]
-    for j in range(len(ctxs)):
-        fetch(j)
-    return outs
+    """integrated gradients of log s(x) for every held-out sample; returns tst.score.token_ig's dict per sample in input order."""
+    return run_heldout(IG, ctx, samples, args)
 
 
 # ---------------------------------------------------------------------------------------------- stacked folds
@@ -509,40 +429,3 @@ def fine_tune_stacked(ctxs, sample_sets, args: TrainArgs, fold_seeds, log=None, 
         import sys
         print(f"[phase] fine_tune_stacked: resets + plans {_t_setup - _t_begin:.3f} s, enqueue loop {_t_enq - _t_setup:.3f} s, final sync {time.perf_counter() - _t_enq:.3f} s", file=sys.stderr)
     return records
-
-
-def score_heldout_stacked(ctxs, sample_sets, args: TrainArgs):
-    """held-out scoring on stacked contexts: batch b of all folds of a context is one forward pass; returns (s, pred, correct)
-    per fold, in the order of sample_sets."""
-    where = place_folds(len(sample_sets), ctxs)
-    bs = args.per_device_eval_batch_size
-    outs = [([], [], []) for _ in sample_sets]
-    pending = [None] * len(ctxs)
-    mine = [[(sl, i) for i, (jj, sl) in enumerate(where) if jj == j] for j in range(len(ctxs))]
-
-    def fetch(j):
-        if pending[j] is not None:
-            parts = pending[j]   # [(fold position, samples)]
-            logp, corr, optl, rseq = ctxs[j].score_rows_fetch()
-            flat = [x for _, b in parts for x in b]
-            s, p, c = S.bias_scores(flat, logp, corr, optl, rseq)
-            o = 0
-            for i, b in parts:
-                outs[i][0].append(s[o:o + len(b)]); outs[i][1].append(p[o:o + len(b)]); outs[i][2].append(c[o:o + len(b)])
-                o += len(b)
-            pending[j] = None
-
-    nb = max((len(smp) + bs - 1) // bs for smp in sample_sets) if sample_sets else 0
-    for b in range(nb):
-        for j, c in enumerate(ctxs):
-            fetch(j)
-            parts = [(sl, i, sample_sets[i][b * bs:(b + 1) * bs]) for sl, i in mine[j]]
-            parts = [(sl, i, x) for sl, i, x in parts if x]
-            if parts:
-                ids, labels, cu, seq_slot = collate_stacked([(sl, x) for sl, _, x in parts])
-                c.score_rows_async(ids, labels, cu, args.option_ids, seq_slot)
-                pending[j] = [(i, x) for _, i, x in parts]
-    for j in range(len(ctxs)):
-        fetch(j)
-    empty_f, empty_i = np.zeros(0, np.float32), np.zeros(0, np.int32)
-    return [(np.concatenate(o[0]) if o[0] else empty_f, np.concatenate(o[1]) if o[1] else empty_i, np.concatenate(o[2]) if o[2] else empty_i) for o in outs]

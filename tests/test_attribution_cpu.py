@@ -145,7 +145,7 @@ class FakeCtx:
 
 
 def test_attribute_heldout_loops_keep_order_batches_kinds_and_slots():
-    from tst.trainer import TrainArgs, attribute_heldout, attribute_heldout_concurrent, attribute_heldout_stacked
+    from tst.trainer import TrainArgs, ATTRIBUTE, attribute_heldout, run_heldout_concurrent, run_heldout_stacked
     args = TrainArgs(per_device_eval_batch_size=4, attribute=True, option_ids=(3, 4))
     sets = [[_sample(100 * f + i, [100 * f + 10 * i, 100 * f + 10 * i + 1], [3], kind="mca" if i % 2 else "na") for i in range(n)] for f, n in enumerate((10, 3, 6))]
     c = FakeCtx()
@@ -154,12 +154,12 @@ def test_attribute_heldout_loops_keep_order_batches_kinds_and_slots():
     assert [list(g["gxi"]) for g in got] == [[10 * i, 10 * i + 1] for i in range(10)]     # the prompt tokens of every sample, in input order
     assert [g["log_s"] for g in got] == [0, -1, -2, -3, 0, -1, -2, -3, 0, -1]
     cs = [FakeCtx() for _ in sets]
-    outs = attribute_heldout_concurrent(cs, sets, args)
+    outs = run_heldout_concurrent(ATTRIBUTE, cs, sets, args)
     assert [[call[0] for call in c.calls] for c in cs] == [[4, 4, 2], [3], [4, 2]]
     for smp, out in zip(sets, outs):
         assert [list(g["gxi"]) for g in out] == [[float(t) for t in x.ids[:2]] for x in smp]
     cs = [FakeCtx(2), FakeCtx(2)]
-    outs = attribute_heldout_stacked(cs, sets, args)
+    outs = run_heldout_stacked(ATTRIBUTE, cs, sets, args)
     assert [call[:2] for call in cs[0].calls] == [(7, (0, 0, 0, 0, 1, 1, 1)), (4, (0, 0, 0, 0)), (2, (0, 0))]
     assert [len(o) for o in outs] == [10, 3, 6]
     assert [list(g["gxi"]) for g in outs[1]] == [[float(t) + 1000 for t in x.ids[:2]] for x in sets[1]]      # fold 1 ran in slot 1

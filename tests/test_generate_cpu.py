@@ -126,7 +126,7 @@ class FakeCtx:
 
 
 def test_generate_heldout_loops_keep_order_batches_and_slots():
-    from tst.trainer import TrainArgs, generate_heldout, generate_heldout_concurrent, generate_heldout_stacked
+    from tst.trainer import TrainArgs, GENERATE, generate_heldout, run_heldout_concurrent, run_heldout_stacked
     args = TrainArgs(per_device_eval_batch_size=4, generate=True, max_new_tokens=3, eos_ids=(1000,))
     # sample i: prompt starts with 100 + 10 i, the reference answer is what FakeCtx says in slot 0
     sets = [[_sample(100 * f + i, [100 + 10 * i + 100 * f, 7], [101 + 10 * i + 100 * f, 102 + 10 * i + 100 * f]) for i in range(n)] for f, n in enumerate((10, 3, 6))]
@@ -136,13 +136,13 @@ def test_generate_heldout_loops_keep_order_batches_and_slots():
     assert [g for g, _ in got] == [[101 + 10 * i, 102 + 10 * i, 103 + 10 * i] for i in range(10)] and all(ok == 1 for _, ok in got)
     # concurrent: one context per fold, every fold's batches in its own order
     cs = [FakeCtx() for _ in sets]
-    outs = generate_heldout_concurrent(cs, sets, args)
+    outs = run_heldout_concurrent(GENERATE, cs, sets, args)
     assert [[n for n, _, _, _ in c.calls] for c in cs] == [[4, 4, 2], [3], [4, 2]]
     for smp, out in zip(sets, outs):
         assert [g[0] for g, _ in out] == [int(x.ids[0]) + 1 for x in smp] and all(ok == 1 for _, ok in out)
     # stacked: folds 0, 1 in the slots of context 0, fold 2 in context 1 (place_folds); the slot shifts FakeCtx's tokens, so slot 1's answers are wrong
     cs = [FakeCtx(2), FakeCtx(2)]
-    outs = generate_heldout_stacked(cs, sets, args)
+    outs = run_heldout_stacked(GENERATE, cs, sets, args)
     assert [call[:2] for call in cs[0].calls] == [(7, (0, 0, 0, 0, 1, 1, 1)), (4, (0, 0, 0, 0)), (2, (0, 0))]
     assert [call[:2] for call in cs[1].calls] == [(4, (0, 0, 0, 0)), (2, (0, 0))]
     assert [len(o) for o in outs] == [10, 3, 6]

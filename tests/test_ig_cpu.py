@@ -153,7 +153,7 @@ class FakeCtx:
 
 
 def test_attribute_ig_heldout_loops_keep_order_batches_kinds_slots_and_baselines():
-    from tst.trainer import TrainArgs, attribute_ig_heldout, attribute_ig_heldout_concurrent, attribute_ig_heldout_stacked
+    from tst.trainer import TrainArgs, IG, attribute_ig_heldout, run_heldout_concurrent, run_heldout_stacked
     args = TrainArgs(per_device_eval_batch_size=4, attribute_ig=8, attribute_baseline_id=7, option_ids=(3, 4))
     assert (args.attribute_ig, args.attribute_baseline_id, args.attribute) == (8, 7, False)
     sets = [[_sample(100 * f + i, [100 * f + 10 * i, 100 * f + 10 * i + 1], [3], kind="mca" if i % 2 else "na") for i in range(n)] for f, n in enumerate((10, 3, 6))]
@@ -165,12 +165,12 @@ def test_attribute_ig_heldout_loops_keep_order_batches_kinds_slots_and_baselines
     assert [g["log_s"] for g in got] == [0, -1, -2, -3, 0, -1, -2, -3, 0, -1] and all(g["log_s_base"] == g["log_s"] - 8 for g in got)
     assert all(g["delta"] == pytest.approx(float(np.sum(g["ig"])) - 8) for g in got)
     cs = [FakeCtx() for _ in sets]
-    outs = attribute_ig_heldout_concurrent(cs, sets, args)
+    outs = run_heldout_concurrent(IG, cs, sets, args)
     assert [[call[0] for call in c.calls] for c in cs] == [[4, 4, 2], [3], [4, 2]]
     for smp, out in zip(sets, outs):
         assert [list(g["ig"]) for g in out] == [[float(t) for t in x.ids[:2]] for x in smp]
     cs = [FakeCtx(2), FakeCtx(2)]
-    outs = attribute_ig_heldout_stacked(cs, sets, args)
+    outs = run_heldout_stacked(IG, cs, sets, args)
     assert [call[:2] for call in cs[0].calls] == [(7, (0, 0, 0, 0, 1, 1, 1)), (4, (0, 0, 0, 0)), (2, (0, 0))]
     assert [len(o) for o in outs] == [10, 3, 6]
     assert [list(g["ig"]) for g in outs[1]] == [[float(t) + 1000 for t in x.ids[:2]] for x in sets[1]]      # fold 1 ran in slot 1
