@@ -1,6 +1,7 @@
 /*
- * libtst_host -- CPU-only C-ABI over the host arithmetic of libtst_hip (test-set-training_amd/csrc/host_logic.h): batch validation and the labelled-row
- * map, the flat layout of a full fine-tune and its gradient regions, the ZeRO-1 shard map, the RoPE inverse frequencies. It is the SAME code the product
+ * libtst_host -- CPU-only C-ABI over the host arithmetic of libtst_hip (test-set-training_amd/csrc/host_logic.h): validation of the configuration and of
+ * every batch, the labelled-row map, the flat layout of a full fine-tune and its gradient regions, the trainable table of the LoRA module groups, the ZeRO-1
+ * shard map, the RoPE inverse frequencies. It is the SAME code the product
  * library runs on its hot path, compiled by g++ without any HIP dependency, so that it can be driven on a CPU box: by the Python CPU tests (the gloo
  * stand-ins for the multi-rank ZeRO step use the product's own shard map and layout) and, built with -fsanitize=address,undefined, by the self-test
  * csrc/host_selftest.cpp (sanitizers run on the CPU build only). TEST / DIAGNOSTIC surface: a maintainer binds include/tst_hip.h.
@@ -29,6 +30,14 @@ int tst_host_decay_split(int64_t lo, int64_t hi, int64_t n_decay, int64_t* out2)
 /* flat layout of a full fine-tune of the configuration. out8 = {n_train, n_decay, per_layer, embed, wpe (-1: none), lm_head, first layer, tail};
  * regions_out (may be NULL) receives up to cap (offset, count) pairs in the order backward finishes them; *n_regions_out their number. */
 int tst_host_full_layout(const tst_model_cfg* cfg, int64_t* out8, int64_t* regions_out, int cap, int* n_regions_out);
+
+/* tsthost::check_cfg: every refusal tst_create (is_fork = 0) or tst_fork (is_fork = 1: the parent's configuration) makes from the configuration alone, in the
+ * engine's order; err_out / err_cap receive the message tst_last_error would report. Returns TST_OK or TST_EINVAL. */
+int tst_host_check_cfg(const tst_model_cfg* cfg, int is_fork, char* err_out, int err_cap);
+/* tsthost::lora_layout: the trainable table of ONE slot of a LoRA context of the configuration, as tst_trainable_info reports it. out3 = {n1 (elements per
+ * slot), n_train (n1 * max(n_stack, 1)), number of entries}; entry i (up to cap; both arrays may be NULL): names_out[i * name_cap ..] its name,
+ * entries_out[3 i ..] = {offset, rows, cols}. */
+int tst_host_lora_layout(const tst_model_cfg* cfg, int64_t* out3, char* names_out, int name_cap, int64_t* entries_out, int cap);
 
 /* tsthost::plan_batch on a caller-provided staging buffer of tst_host_stage_ints(...) ints laid out ids[max_tokens] | pos[max_tokens] | cu[max_seqs + 1] |
  * lab_idx[max_labelled] | targets[max_labelled]. out_ints[4 + 8 + 9 + 8] = {T_dev, S, R, maxlen, slot_t_end[8], slot_r0[9], row_end[8]}; row_seq_out

@@ -77,10 +77,12 @@ inline hipStream_t masked_stream(int device, int n_cus) {
   return s;
 }
 
-inline bool env_flag(const char* name, bool dflt) {
+// every TST_* integer / boolean switch of this file: unset = the default, else atoi
+inline int env_int(const char* name, int dflt) {
   const char* e = getenv(name);
-  return e ? atoi(e) != 0 : dflt;
+  return e ? atoi(e) : dflt;
 }
+inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt) != 0; }
 // the attention kernels take a sequence's workgroups longest sequence first (plan_batch's order vector); TST_ATTN_ORDER=0: batch order (A/B switch; no output depends on it)
 inline bool attn_order_on() {
   static const bool on = env_flag("TST_ATTN_ORDER", true);
@@ -153,10 +155,7 @@ struct LayerT {
   float *rstd1, *rstd2, *lse;
 };
 
-struct TrainableInfo {
-  std::string name;
-  int64_t offset, rows, cols;
-};
+using TrainableInfo = tsthost::TrainableEntry;   // (name, offset, rows, cols): host_logic.h states the LoRA table
 
 }  // namespace
 
@@ -238,7 +237,8 @@ struct tst_ctx {
   // laid out exactly like the fp32 master tp (matrices first = decay group, then norm vectors = no-decay group), so the
   // optimizer kernel refreshes it element for element; wb0 = pristine snapshot restored at the start of each fold.
   bool full = false;
-  int64_t n_decay = 0;
+  int64_t n_decay = 0, per_layer = 0;   // (host_logic.h full_layout: the decay group's length, one layer's four matrices)
+  tsthost::ModelDims md;                // host_logic.h model_dims of cfg: what the fields above restate, and qkv_bias
   // trainables
   int64_t n_train = 0;
   float *tp = nullptr, *tg = nullptr, *tm = nullptr, *tv = nullptr;
@@ -252,7 +252,7 @@ struct tst_ctx {
   SlotEnds slot_ends;                    // current batch: tokens of slot s end at slot_ends.t_end[s]
   SlotEnds row_ends;                     // current batch: labelled rows of slot s end at row_ends.t_end[s] (slot boundaries of the compacted last layer's rows)
   bool trim_last = env_flag("TST_TRIM_LAST", true);   // "trim_last_token" (include/tst_hip.h tst_set_option; env TST_TRIM_LAST=0 starts with it off)
-  int swr = [] { const char* e = getenv("TST_SWR"); return e ? atoi(e) & 3 : 3; }();   // "swiglu_rank": bit 0 the forward, bit 1 the backward fused SwiGLU + rank kernel (env TST_SWR)
+  int swr = env_int("TST_SWR", 3) & 3;   // "swiglu_rank": bit 0 the forward, bit 1 the backward fused SwiGLU + rank kernel (env TST_SWR)
   bool lc_have = false, lc_on = false, lc_used = false, lc_batch_ok = true;   // last-layer compaction (see lc_attn below): workspace there / switched on / this batch
   int slot_r0[TST_MAX_STACK + 1] = {0};  // current batch: labelled rows of slot s are [slot_r0[s], slot_r0[s+1])
   std::vector<TrainableInfo> tinfo;
@@ -331,8 +331,8 @@ struct tst_ctx {
   // the ONE stored W (NN) -- no W^T copies in HBM, AdamW writes 30 instead of 32 B / param; bit 1 ("kmajor_dw"): dW = dy^T . x straight from the row-major
   // activations (TN) -- no transposed activation copies. "kmajor" (tst_set_option) reads both bits
   int kmajor = 0;
-  int nbdw = [] { const char* e = getenv("TST_NBDW"); return e ? atoi(e) : 1; }();   // "norm_bwd_dw" (tst_set_option): full fine-tune, RMSNorm backward + its weight gradient in one pass
-  int nrk = [] { const char* e = getenv("TST_NRK"); return e ? atoi(e) : 1; }();   // "norm_rank" (tst_set_option): RMSNorm forward fused with the rank-axis contraction behind it
+  int nbdw = env_int("TST_NBDW", 1);   // "norm_bwd_dw" (tst_set_option): full fine-tune, RMSNorm backward + its weight gradient in one pass
+  int nrk = env_int("TST_NRK", 1);   // "norm_rank" (tst_set_option): RMSNorm forward fused with the rank-axis contraction behind it
   // "ndw_side" (tst_set_option): a full fine-tune's norm-weight reductions beside the weight gradients on the side stream. OFF by default: measured -1.1 %
   // (24.12 -> 23.85 QA-pairs/s, two interleaved rounds, profiles/r05_full_ndw_side_ab.txt) -- as in round 4, when the side stream was the longer one
   bool ndw_side = env_flag("TST_NDW_SIDE", false);
@@ -378,7 +378,7 @@ struct CtxT : tst_ctx {
   AT *xg = nullptr, *xf = nullptr, *dxf = nullptr, *dxg = nullptr, *dlogits = nullptr;
   // backward scratch
   AT *dX = nullptr, *dH = nullptr, *dxn = nullptr, *dattn_b = nullptr, *dqkv_b = nullptr, *dact = nullptr, *dgu = nullptr;
-  AT *du = nullptr, *duT = nullptr, *usT = nullptr, *dyT = nullptr, *xT = nullptr;
+  AT *du = nullptr, *dyT = nullptr, *xT = nullptr;
   AT* du4[4] = {nullptr, nullptr, nullptr, nullptr};
   // Last-layer compaction (LoRA; TST_LAST_COMPACT, default on): behind the last layer's attention only the rows the head reads (labelled / selected rows,
   // d_lab_idx) are ever used -- o projection, MLP and their backward are row-wise -- so those run on the R gathered rows instead of all T tokens
@@ -550,7 +550,7 @@ int ctx_event_sync(tst_ctx* ctx, hipEvent_t ev) {
 #ifdef TST_BUILD_LAB
 std::atomic<int> g_whatif_live{0};   // (contexts may step from several host threads)
 inline int whatif() {
-  static const int m = [] { const char* e = getenv("TST_WHATIF"); return e ? atoi(e) : 0; }();
+  static const int m = env_int("TST_WHATIF", 0);
   return g_whatif_live.load(std::memory_order_relaxed) >= 12 ? m : 0;
 }
 inline void whatif_tick() { if (g_whatif_live.load(std::memory_order_relaxed) < 12) g_whatif_live.fetch_add(1, std::memory_order_relaxed); }
@@ -590,7 +590,7 @@ int run_gemm(CtxT<AT>* ctx, GemmParamsT<AT> p, bool on_side = false) {
   // of the last partial wave of tiles + a reduce launch) then only adds traffic: 22.9 -> 23.4 QA-pairs/s without it (profiles/r05_full_tail_split_ab.txt)
   if (ctx->full) {
     p.no_tail = 1;
-    static const int fsk = [] { const char* e = getenv("TST_FULL_SPLITK"); return e ? atoi(e) : 2; }();   // A/B: bit 0 = split-K in the forward (under AdamW the slabs add HBM traffic to the saturated side), bit 1 = in the backward; 2: profiles/r05_full_splitk_ab.txt
+    static const int fsk = env_int("TST_FULL_SPLITK", 2);   // A/B: bit 0 = split-K in the forward (under AdamW the slabs add HBM traffic to the saturated side), bit 1 = in the backward; 2: profiles/r05_full_splitk_ab.txt
     if (!(fsk & (ctx->in_backward ? 2 : 1))) p.no_splitk = 1;
   }
   int rc = gemm_nt(gst, p, on_side ? ctx->side_slab : ctx->slab, on_side ? ctx->side_slab_bytes : ctx->slab_bytes, -1, -1, used);
@@ -722,7 +722,7 @@ int linear_fwd(CtxT<AT>* ctx, const AT* x, const ProjT<AT>& P, AT* us, const AT*
 // launch (or on the side stream) every group keeps its own buffer until that launch has run
 template <typename AT>
 AT* du_target(CtxT<AT>* ctx, const LoraGroupT<AT>& g, int slot, bool* grouped_out = nullptr, bool* on_side_out = nullptr) {
-  static const bool group_env = [] { const char* e = getenv("TST_TN_GROUPED"); return !e || atoi(e) != 0; }();   // A/B switch
+  static const bool group_env = env_flag("TST_TN_GROUPED", true);   // A/B switch
   const bool grouped = group_env && sizeof(AT) == 2 && g.on && ctx->du4[0] != nullptr;
   // the side stream pays only when the fold has the GPU to itself (tile policy 3: +3.5 % at one fold per GPU); with resident
   // folds the extra streams cost 14 % (97.2 -> 83.4 QA-pairs/s with three folds), like a fourth fold does
@@ -732,12 +732,6 @@ AT* du_target(CtxT<AT>* ctx, const LoraGroupT<AT>& g, int slot, bool* grouped_ou
   return (on_side || grouped) ? ctx->du4[slot] : ctx->du;
 }
 
-// elements of one layer's four projection matrices: a layer's share of the flat buffer of a full fine-tune
-inline int64_t layer_numel(const tst_ctx* ctx) {
-  int64_t n = 0;
-  for (int p = 0; p < 4; ++p) n += (int64_t)ctx->proj_dout[p] * ctx->proj_din[p];
-  return n;
-}
 // sums-of-squares slots of one weight-gradient matrix (tst_ctx::gn_partial): one per 256x256 tile + 16 per possible tail tile (at most 128)
 inline int64_t gn_slots(int dout, int din) { return (int64_t)tst_ceil_div(dout, 256) * tst_ceil_div(din, 256) + 2048; }
 
@@ -809,7 +803,7 @@ int linear_bwd(CtxT<AT>* ctx, const AT* dy, const AT* x, const ProjT<AT>& P, con
     // dBg[dout,RP] = dy^T . us ;  dAg[RP,din] = s * du^T . x
     // the slot-restricted launch (gemm_tns.hip) instead of general 128 x 128 TN tiles over all tokens and all RP columns; TST_TN_SLOT=0 restores those
     // (A/B, profiles/r03_ab_tn_slot.txt: +0.4 ... +0.8 % with two streams, +1.4 % with one)
-    static const bool tns_env = [] { const char* e = getenv("TST_TN_SLOT"); return !e || atoi(e) != 0; }();
+    static const bool tns_env = env_flag("TST_TN_SLOT", true);
     bool tns = false;
     if constexpr (sizeof(AT) == 2) {
       if (grouped && tns_env && ((g.d.nmod * g.d.r) & 7) == 0) {
@@ -845,7 +839,7 @@ int linear_bwd(CtxT<AT>* ctx, const AT* dy, const AT* x, const ProjT<AT>& P, con
     if (!P.WT) {   // full fine-tune without W^T copies (ctx->kmajor bit 0): dx = dy . W on the NN member, W[dout][din] as it is stored
       GemmParams q = gp<AT>(dy, dout, P.W, din, dx, din, T, din, dout);
       q.tb = 1; q.no_tail = 1;
-      static const int fsk = [] { const char* e = getenv("TST_FULL_SPLITK"); return e ? atoi(e) : 2; }();
+      static const int fsk = env_int("TST_FULL_SPLITK", 2);
       if (!(fsk & 2)) q.no_splitk = 1;
       return run_gemm_kmajor(ctx, q, false, -1, 2.0 * T * din * (double)dout, "NN", true);
     }
@@ -1436,47 +1430,6 @@ int refresh_transposes(CtxT<AT>* ctx) {
   return TST_OK;
 }
 
-template <typename AT>
-int add_group(CtxT<AT>* ctx, int layer, LoraGroupT<AT>& g, int din, int dout, const char* const* names, const int* row0, const int* row1, const bool* on, int nmod) {
-  const int r = ctx->cfg.lora_r;
-  int nseg = 0;   // enabled modules of the group; slot 0's offsets are set here, the other slots' by build_ctx once n1 is known
-  LoraGroupDescT<AT> dsc;
-  memset(&dsc, 0, sizeof(dsc));
-  for (int m = 0; m < nmod; ++m) {
-    if (!on[m]) continue;
-    dsc.seg_row0[nseg] = row0[m];
-    dsc.seg_row1[nseg] = row1[m];
-    const int rows = row1[m] - row0[m];
-    dsc.a_off[nseg] = ctx->n_train;
-    ctx->tinfo.push_back({std::string("layers.") + std::to_string(layer) + "." + names[m] + ".lora_A", ctx->n_train, r, din});
-    ctx->n_train += (int64_t)r * din;
-    dsc.b_off[nseg] = ctx->n_train;
-    ctx->tinfo.push_back({std::string("layers.") + std::to_string(layer) + "." + names[m] + ".lora_B", ctx->n_train, rows, r});
-    ctx->n_train += (int64_t)rows * r;
-    ++nseg;
-  }
-  if (nseg == 0) { g.on = false; return TST_OK; }
-  dsc.din = din; dsc.dout = dout; dsc.r = r; dsc.nmod = nseg; dsc.nslot = ctx->ns; dsc.nseg = nseg * ctx->ns;
-  dsc.RP = roundup(dsc.nseg * r, 64);
-  dsc.scale = ctx->cfg.lora_alpha / (float)r;
-  dsc.Ag = palloc<AT>(ctx, (int64_t)dsc.RP * din);
-  dsc.AgT = palloc<AT>(ctx, (int64_t)din * dsc.RP);
-  dsc.Bg = palloc<AT>(ctx, (int64_t)dout * dsc.RP);
-  dsc.BgT = palloc<AT>(ctx, (int64_t)dsc.RP * dout);
-  dsc.dAg = palloc<float>(ctx, (int64_t)dsc.RP * din);
-  dsc.dBg = palloc<float>(ctx, (int64_t)dout * dsc.RP);
-  if (!dsc.Ag || !dsc.AgT || !dsc.Bg || !dsc.BgT || !dsc.dAg || !dsc.dBg) return TST_ENOMEM;
-  g.on = true;
-  g.d = dsc;
-  g.index = (int)ctx->descs.size();
-  ctx->descs.push_back(dsc);
-  const long elems = (long)dsc.RP * din + (long)dout * dsc.RP;
-  if (elems > ctx->pack_max_elems) ctx->pack_max_elems = elems;
-  if (din > ctx->pack_max_long) ctx->pack_max_long = din;
-  if (dout > ctx->pack_max_long) ctx->pack_max_long = dout;
-  return TST_OK;
-}
-
 // HF state_dict name -> its entry in the context's table (nullptr: the family has no such tensor)
 template <typename AT>
 const typename CtxT<AT>::Named* find_weight(const CtxT<AT>* ctx, const char* name) {
@@ -1542,204 +1495,196 @@ void name_tensors_gpt2(CtxT<AT>* ctx) {
   }
 }
 
+// ---- construction. build_ctx (below) is the list of these stages; their order is the order of the device allocations, and addresses follow it.
+#define ALLOC(dst, type, count) \
+  do { dst = palloc<type>(ctx, (int64_t)(count)); if (!dst) return fail(ctx, TST_ENOMEM, "hipMalloc failed: " #dst); } while (0)
+
+inline int head_rows(const tst_ctx* ctx) { return roundup(ctx->Rmax, 64); }   // whole 64-row k-steps are readable (lm_head dW contracts over the labelled rows)
 template <typename AT>
-int build_ctx(CtxT<AT>* ctx) {
+int rank_pad_max(const CtxT<AT>* ctx) {   // widest padded rank block of any module group (groups are padded to multiples of 64, at most 3 * 64)
+  int rp = 64;
+  for (auto& g : ctx->descs) if (g.RP > rp) rp = g.RP;
+  return rp;
+}
+// LoRA: the adapter-gradient contractions get a side stream unless TST_NO_SIDE_STREAM; a full fine-tune's weight gradients always run beside the dX chain
+inline bool wants_side_stream(const tst_ctx* ctx) {
+  if (ctx->full) return true;
+  static const bool no_side = env_flag("TST_NO_SIDE_STREAM", false);
+  return !no_side;
+}
+// dimensions, stated once: host_logic.h model_dims and (full fine-tune) full_layout; the configuration has passed check_cfg
+template <typename AT>
+int set_dims(CtxT<AT>* ctx) {
   const tst_model_cfg& c = ctx->cfg;
-  ctx->d = c.hidden_size; ctx->L = c.num_layers; ctx->H = c.num_heads; ctx->Hkv = c.num_kv_heads; ctx->dh = c.head_dim;
-  ctx->F = c.intermediate_size; ctx->V = c.vocab_size;
-  ctx->gpt2 = (c.arch == TST_ARCH_GPT2);
-  ctx->qk_norm = (c.arch == TST_ARCH_QWEN3);
-  ctx->Vp = roundup(ctx->V, 64);
-  ctx->Fgu = ctx->gpt2 ? ctx->F : 2 * ctx->F;
-  ctx->npos = c.max_position;
-  ctx->dq = ctx->H * ctx->dh; ctx->dkv = ctx->Hkv * ctx->dh; ctx->dqkv = ctx->dq + 2 * ctx->dkv; ctx->dattn = ctx->dq;
+  const tsthost::ModelDims m = ctx->md = tsthost::model_dims(c);
+  ctx->d = m.d; ctx->L = m.L; ctx->F = m.F; ctx->Fgu = m.Fgu; ctx->Vp = m.V; ctx->npos = m.npos; ctx->dh = m.dh; ctx->gpt2 = m.gpt2; ctx->qk_norm = m.qk_norm;
+  ctx->dq = m.dq; ctx->dkv = m.dkv; ctx->dqkv = m.dqkv; ctx->dattn = m.dattn; ctx->H = c.num_heads; ctx->Hkv = c.num_kv_heads; ctx->V = c.vocab_size;
   ctx->Tmax = c.max_tokens; ctx->Smax = c.max_seqs; ctx->Rmax = c.max_labelled;
-  ctx->Tpad_max = roundup(ctx->Tmax, 64);
-  {   // a layer's four projections [dout, din]: q|k|v, o, gate|up (GPT-2: c_fc), down
-    const int pd[4][2] = {{ctx->dqkv, ctx->d}, {ctx->d, ctx->dattn}, {ctx->Fgu, ctx->d}, {ctx->d, ctx->F}};
-    for (int p = 0; p < 4; ++p) { ctx->proj_dout[p] = pd[p][0]; ctx->proj_din[p] = pd[p][1]; }
-  }
   // every [tokens, .] buffer has Tpad_max rows: the TN contractions read whole 64-row k-steps (rows >= n_tokens are
-  // masked in-kernel but must be readable and finite, hence the zero fill below)
-  const int d = ctx->d, F = ctx->F, V = ctx->Vp, L = ctx->L, T = ctx->Tpad_max, Tp = ctx->Tpad_max, Fgu = ctx->Fgu;
-  const bool gpt2 = ctx->gpt2;
-  if (c.arch != TST_ARCH_LLAMA && c.arch != TST_ARCH_QWEN2 && c.arch != TST_ARCH_QWEN3 && !gpt2) return fail(ctx, TST_EINVAL, "unsupported arch");
-  const bool qk_norm = ctx->qk_norm;
-  const bool qkv_bias = (c.arch == TST_ARCH_QWEN2) || gpt2;
-  if (gpt2 && ctx->Hkv != ctx->H) return fail(ctx, TST_EINVAL, "GPT-2: num_kv_heads must equal num_heads");
-  if (gpt2 && ctx->dq != ctx->d) return fail(ctx, TST_EINVAL, "GPT-2: num_heads * head_dim must equal hidden_size");
-  if (c.train_mode != TST_TRAIN_LORA && c.train_mode != TST_TRAIN_FULL) return fail(ctx, TST_EINVAL, "train_mode must be TST_TRAIN_LORA or TST_TRAIN_FULL");
+  // masked in-kernel but must be readable and finite, hence the pool's zero fill)
+  ctx->Tpad_max = roundup(ctx->Tmax, 64);
+  tsthost::proj_dims(m, ctx->proj_dout, ctx->proj_din);
   ctx->full = (c.train_mode == TST_TRAIN_FULL);
-  if (ctx->full && ctx->parent) return fail(ctx, TST_EINVAL, "full fine-tune contexts cannot be forked (every fold owns its weights)");
-  if (ctx->dh != 128 && !(gpt2 && ctx->dh == 64)) return fail(ctx, TST_EINVAL, "head_dim must be 128 (GPT-2 family: 64 or 128)");
-  if (d % 64 || F % 64 || ctx->dq % 64 || ctx->dkv % 64) return fail(ctx, TST_EINVAL, "hidden/intermediate/head sizes must be multiples of 64");
-  if (ctx->H % ctx->Hkv) return fail(ctx, TST_EINVAL, "num_heads must be a multiple of num_kv_heads");
-  if (T <= 0 || ctx->Smax <= 0 || ctx->Rmax <= 0 || c.max_position <= 0) return fail(ctx, TST_EINVAL, "max_tokens/max_seqs/max_labelled/max_position must be > 0");
-  if (!ctx->full && (c.lora_r <= 0 || c.lora_r > 64 || (64 % c.lora_r) != 0)) return fail(ctx, TST_EINVAL, "lora_r must divide 64");
-  if (!gpt2 && c.rope_scaling != TST_ROPE_DEFAULT) {
-    if (c.rope_scaling != TST_ROPE_LINEAR && c.rope_scaling != TST_ROPE_LLAMA3) return fail(ctx, TST_EINVAL, "rope_scaling must be TST_ROPE_DEFAULT, TST_ROPE_LINEAR or TST_ROPE_LLAMA3");
-    if (!(c.rope_factor > 0.f)) return fail(ctx, TST_EINVAL, "rope_factor must be > 0");
-    if (c.rope_scaling == TST_ROPE_LLAMA3 && (!(c.rope_low_freq_factor > 0.f) || !(c.rope_high_freq_factor > c.rope_low_freq_factor) || c.rope_original_max_position <= 0))
-      return fail(ctx, TST_EINVAL, "llama3 rope scaling needs 0 < rope_low_freq_factor < rope_high_freq_factor and rope_original_max_position > 0");
-  }
   if constexpr (sizeof(AT) == 2) {
     // K-major members for the full fine-tune's backward (tst_ctx::kmajor). Every contraction axis they meet (d_qkv, d, F or 2F, the padded vocabulary) is a
-    // multiple of 64 and every free axis a multiple of 8 by the checks above. TST_KMAJOR = 0 / 1 / 2 / 3 (default 3) is the A/B switch; bit 0 decides what
+    // multiple of 64 and every free axis a multiple of 8 by check_cfg. TST_KMAJOR = 0 / 1 / 2 / 3 (default 3) is the A/B switch; bit 0 decides what
     // is ALLOCATED (no W^T copies), so it is fixed here
-    static const int km_env = [] { const char* e = getenv("TST_KMAJOR"); return e ? atoi(e) : 3; }();
+    static const int km_env = env_int("TST_KMAJOR", 3);
     ctx->kmajor = ctx->full ? (km_env & 3) : 0;
   }
   ctx->ns = c.n_stack > 1 ? c.n_stack : 1;
-  if (ctx->ns > TST_MAX_STACK) return fail(ctx, TST_EINVAL, "n_stack must be <= 8");
-  if (ctx->ns > 1 && ctx->full) return fail(ctx, TST_EINVAL, "stacked folds need frozen base weights (LoRA): a full fine-tune owns its weights");
-  if (ctx->ns > 1 && (c.lora_r & 7)) return fail(ctx, TST_EINVAL, "stacked folds: lora_r must be a multiple of 8");
-  if (ctx->ns > 1 && ctx->strict) return fail(ctx, TST_EINVAL, "stacked folds are a bf16-path feature: precision = strict runs one fold per context");
   ctx->zero_on = c.zero_ranks >= 1;
   ctx->zero = ctx->zero_on ? c.zero_ranks : 1;
   ctx->zero_rank = ctx->zero_on ? c.zero_rank : 0;
-  if (ctx->zero_on && !ctx->full) return fail(ctx, TST_EINVAL, "optimizer-state sharding (zero_ranks >= 1) is for full fine-tunes: LoRA state is 0.2 % of the model");
-  if (ctx->zero_on && (ctx->zero_rank < 0 || ctx->zero_rank >= ctx->zero || ctx->zero > 64)) return fail(ctx, TST_EINVAL, "zero_rank must be in [0, zero_ranks), zero_ranks <= 64");
-
-#define ALLOC(dst, type, count)                                         \
-  do {                                                                  \
-    dst = palloc<type>(ctx, (int64_t)(count));                          \
-    if (!dst) return fail(ctx, TST_ENOMEM, "hipMalloc failed: " #dst);  \
-  } while (0)
-
-  const CtxT<AT>* sh = ctx->parent;  // fork: frozen weights and RoPE tables are the parent's (one copy in HBM for all folds)
-  // full fine-tune: one flat bf16 buffer in the master's order: [embed | per layer Wqkv, Wo, Wgu, Wd | lm_head | norms]
-  int64_t wofs = 0;
-  auto take = [&](int64_t n) { AT* p = ctx->wb + wofs; wofs += n; return p; };
-  if (ctx->full) {
-    const int64_t per_layer = layer_numel(ctx);
-    // GPT-2: one tied [V, d] matrix + wpe; per layer 2 LayerNorms with bias and 4 Conv1D biases, + ln_f
-    ctx->n_decay = (gpt2 ? (int64_t)V * d + (int64_t)ctx->npos * d : 2 * (int64_t)V * d) + L * per_layer;
-    ctx->n_train = ctx->n_decay + (gpt2 ? (int64_t)L * (4 * d + ctx->dqkv + d + Fgu + d) + 2 * d
-                                         : (int64_t)(2 * L + 1) * d + (qkv_bias ? (int64_t)L * ctx->dqkv : 0) + (qk_norm ? (int64_t)L * 2 * ctx->dh : 0));
-    if (ctx->zero_on) {
-      const tsthost::ZeroShard z = tsthost::zero_shard(ctx->n_train, ctx->zero, ctx->zero_rank);   // (host_logic.h)
-      ctx->n_pad = z.n_pad; ctx->z_shard = z.shard; ctx->z_lo = z.lo; ctx->z_hi = z.hi;
-    } else {
-      ctx->n_pad = ctx->n_train; ctx->z_lo = 0; ctx->z_hi = ctx->n_train; ctx->z_shard = ctx->n_train;
-    }
-    ALLOC(ctx->wb, AT, ctx->n_pad);     // (all-gather target: zero_ranks equal shards)
-    ALLOC(ctx->wb0, AT, ctx->n_train);
-    ctx->embed = take((int64_t)V * d);
-    if (gpt2) ctx->wpe = take((int64_t)ctx->npos * d);
-    if (!(ctx->kmajor & 1)) ALLOC(ctx->lm_headT, AT, (int64_t)V * d);
-  } else if (sh) {
-    ctx->embed = sh->embed; ctx->lm_head = sh->lm_head; ctx->lm_headT = sh->lm_headT; ctx->final_norm = sh->final_norm;
-    ctx->wpe = sh->wpe; ctx->final_norm_b = sh->final_norm_b;
-  } else {
-    ALLOC(ctx->embed, AT, (int64_t)V * d);
-    if (gpt2) {
-      ctx->lm_head = ctx->embed;  // tied head
-      ALLOC(ctx->wpe, AT, (int64_t)ctx->npos * d);
-      ALLOC(ctx->final_norm_b, AT, d);
-    } else {
-      ALLOC(ctx->lm_head, AT, (int64_t)V * d);
-    }
-    ALLOC(ctx->lm_headT, AT, (int64_t)V * d);
-    ALLOC(ctx->final_norm, AT, d);
+  if (!ctx->full) return TST_OK;
+  const tsthost::FullLayout fl = tsthost::full_layout(m);
+  ctx->n_decay = fl.n_decay; ctx->n_train = fl.n_train; ctx->per_layer = fl.per_layer;
+  ctx->n_pad = ctx->n_train; ctx->z_lo = 0; ctx->z_hi = ctx->n_train; ctx->z_shard = ctx->n_train;
+  if (ctx->zero_on) {
+    const tsthost::ZeroShard z = tsthost::zero_shard(ctx->n_train, ctx->zero, ctx->zero_rank);   // (host_logic.h)
+    ctx->n_pad = z.n_pad; ctx->z_shard = z.shard; ctx->z_lo = z.lo; ctx->z_hi = z.hi;
   }
-  ctx->layers.resize(L);
-  static const char* n_qkv[3] = {"q_proj", "k_proj", "v_proj"};
-  static const char* n_o[1] = {"o_proj"};
-  static const char* n_gu[2] = {"gate_proj", "up_proj"};
-  static const char* n_d[1] = {"down_proj"};
-  static const char* g_qkv[1] = {"attn.c_attn"};
-  static const char* g_o[1] = {"attn.c_proj"};
-  static const char* g_fc[1] = {"mlp.c_fc"};
-  static const char* g_d[1] = {"mlp.c_proj"};
-  for (int l = 0; l < L; ++l) {
-    LayerT<AT>& W = ctx->layers[l];
+  return TST_OK;
+}
+// Weight storage, one of three. Full fine-tune: one flat buffer in the master's order [embed | per layer Wqkv, Wo, Wgu, Wd | lm_head | norms], every tensor a
+// slice of it. Fork: the frozen weights are the parent's (one copy in HBM for all folds). Root: one allocation per tensor. A layer's OWN allocations
+// (layer_weights) are made layer by layer, between the previous layer's stash and this layer's module groups.
+template <typename AT>
+int weight_storage(CtxT<AT>* ctx) {
+  const int d = ctx->d, V = ctx->Vp, Fgu = ctx->Fgu;
+  const bool gpt2 = ctx->gpt2, qk_norm = ctx->qk_norm, qkv_bias = ctx->md.qkv_bias;
+  ctx->layers.resize(ctx->L);
+  for (auto& W : ctx->layers) {
     const LoraGroupT<AT>* const groups[4] = {&W.g_qkv, &W.g_o, &W.g_gu, &W.g_d};
     for (int p = 0; p < 4; ++p) { W.proj[p].dout = ctx->proj_dout[p]; W.proj[p].din = ctx->proj_din[p]; W.proj[p].g = groups[p]; }
-    if (ctx->full) {
-      for (auto& P : W.proj) {
-        P.W = take(P.numel());
-        if (!(ctx->kmajor & 1)) ALLOC(P.WT, AT, P.numel());   // (else dX = dY . W on the NN member: one copy of every weight)
-      }
-    } else if (sh) {
+  }
+  if (const CtxT<AT>* sh = ctx->parent) {
+    ctx->embed = sh->embed; ctx->lm_head = sh->lm_head; ctx->lm_headT = sh->lm_headT; ctx->final_norm = sh->final_norm; ctx->wpe = sh->wpe; ctx->final_norm_b = sh->final_norm_b;
+    for (int l = 0; l < ctx->L; ++l) {
+      LayerT<AT>& W = ctx->layers[l];
       const LayerT<AT>& S = sh->layers[l];
-      W.attn_norm = S.attn_norm; W.mlp_norm = S.mlp_norm; W.bqkv = S.bqkv;
-      W.q_norm = S.q_norm; W.k_norm = S.k_norm;
+      W.attn_norm = S.attn_norm; W.mlp_norm = S.mlp_norm; W.bqkv = S.bqkv; W.q_norm = S.q_norm; W.k_norm = S.k_norm;
       W.attn_norm_b = S.attn_norm_b; W.mlp_norm_b = S.mlp_norm_b; W.bo = S.bo; W.bgu = S.bgu; W.bd = S.bd;
       for (int p = 0; p < 4; ++p) { W.proj[p].W = S.proj[p].W; W.proj[p].WT = S.proj[p].WT; }
-    } else {
-      ALLOC(W.attn_norm, AT, d); ALLOC(W.mlp_norm, AT, d);
-      if (qkv_bias) ALLOC(W.bqkv, AT, ctx->dqkv);
-      if (qk_norm) { ALLOC(W.q_norm, AT, ctx->dh); ALLOC(W.k_norm, AT, ctx->dh); }
-      if (gpt2) {
-        ALLOC(W.attn_norm_b, AT, d); ALLOC(W.mlp_norm_b, AT, d);
-        ALLOC(W.bo, AT, d); ALLOC(W.bgu, AT, Fgu); ALLOC(W.bd, AT, d);
-      }
-      for (auto& P : W.proj) { ALLOC(P.W, AT, P.numel()); ALLOC(P.WT, AT, P.numel()); }
     }
-    const unsigned t = ctx->full ? 0u : c.lora_targets;
+    return TST_OK;
+  }
+  if (!ctx->full) {
+    ALLOC(ctx->embed, AT, (int64_t)V * d);
+    if (gpt2) { ctx->lm_head = ctx->embed; ALLOC(ctx->wpe, AT, (int64_t)ctx->npos * d); ALLOC(ctx->final_norm_b, AT, d); }   // tied head
+    else ALLOC(ctx->lm_head, AT, (int64_t)V * d);
+    ALLOC(ctx->lm_headT, AT, (int64_t)V * d);
+    ALLOC(ctx->final_norm, AT, d);
+    return TST_OK;
+  }
+  ALLOC(ctx->wb, AT, ctx->n_pad);     // (all-gather target: zero_ranks equal shards)
+  ALLOC(ctx->wb0, AT, ctx->n_train);
+  int64_t wofs = 0;
+  auto take = [&](int64_t n) { AT* p = ctx->wb + wofs; wofs += n; return p; };
+  ctx->embed = take((int64_t)V * d);
+  if (gpt2) ctx->wpe = take((int64_t)ctx->npos * d);
+  for (auto& W : ctx->layers)
+    for (auto& P : W.proj) P.W = take(P.numel());
+  if (gpt2) ctx->lm_head = ctx->embed;  // tied head: one parameter, its gradient is the sum of both uses
+  else ctx->lm_head = take((int64_t)V * d);
+  // the no-decay tail, layer by layer: norm vectors and biases (GPT-2: 2 LayerNorms with bias and 4 Conv1D biases, + ln_f)
+  for (auto& W : ctx->layers) {
     if (gpt2) {
-      // peft targets of GPT-2 are the four Conv1D modules: c_attn (any of Q/K/V), attn.c_proj (O), c_fc (GATE/UP), mlp.c_proj (DOWN)
-      { const int r0[1] = {0}, r1[1] = {ctx->dqkv}; const bool on[1] = {(t & (TST_LORA_Q | TST_LORA_K | TST_LORA_V)) != 0};
-        CTX_RC(add_group(ctx, l, W.g_qkv, d, ctx->dqkv, g_qkv, r0, r1, on, 1)); }
-      { const int r0[1] = {0}, r1[1] = {d}; const bool on[1] = {(t & TST_LORA_O) != 0};
-        CTX_RC(add_group(ctx, l, W.g_o, ctx->dattn, d, g_o, r0, r1, on, 1)); }
-      { const int r0[1] = {0}, r1[1] = {F}; const bool on[1] = {(t & (TST_LORA_GATE | TST_LORA_UP)) != 0};
-        CTX_RC(add_group(ctx, l, W.g_gu, d, F, g_fc, r0, r1, on, 1)); }
-      { const int r0[1] = {0}, r1[1] = {d}; const bool on[1] = {(t & TST_LORA_DOWN) != 0};
-        CTX_RC(add_group(ctx, l, W.g_d, F, d, g_d, r0, r1, on, 1)); }
-    } else {
-      {
-        const int r0[3] = {0, ctx->dq, ctx->dq + ctx->dkv}, r1[3] = {ctx->dq, ctx->dq + ctx->dkv, ctx->dqkv};
-        const bool on[3] = {(t & TST_LORA_Q) != 0, (t & TST_LORA_K) != 0, (t & TST_LORA_V) != 0};
-        CTX_RC(add_group(ctx, l, W.g_qkv, d, ctx->dqkv, n_qkv, r0, r1, on, 3));
-      }
-      { const int r0[1] = {0}, r1[1] = {d}; const bool on[1] = {(t & TST_LORA_O) != 0};
-        CTX_RC(add_group(ctx, l, W.g_o, ctx->dattn, d, n_o, r0, r1, on, 1)); }
-      { const int r0[2] = {0, F}, r1[2] = {F, 2 * F}; const bool on[2] = {(t & TST_LORA_GATE) != 0, (t & TST_LORA_UP) != 0};
-        CTX_RC(add_group(ctx, l, W.g_gu, d, 2 * F, n_gu, r0, r1, on, 2)); }
-      { const int r0[1] = {0}, r1[1] = {d}; const bool on[1] = {(t & TST_LORA_DOWN) != 0};
-        CTX_RC(add_group(ctx, l, W.g_d, F, d, n_d, r0, r1, on, 1)); }
+      W.attn_norm = take(d); W.attn_norm_b = take(d); W.mlp_norm = take(d); W.mlp_norm_b = take(d);
+      W.bqkv = take(ctx->dqkv); W.bo = take(d); W.bgu = take(Fgu); W.bd = take(d);
+      continue;
     }
+    W.attn_norm = take(d); W.mlp_norm = take(d);
+    if (qkv_bias) W.bqkv = take(ctx->dqkv);
+    // Qwen3 head-norm vectors: with the other norm vectors in the no-decay tail (HF's Trainer excludes every "_norm" parameter from decay)
+    if (qk_norm) { W.q_norm = take(ctx->dh); W.k_norm = take(ctx->dh); }
+  }
+  ctx->final_norm = take(d);
+  if (gpt2) ctx->final_norm_b = take(d);
+  if (wofs != ctx->n_train) return fail(ctx, TST_ESTATE, "internal: full fine-tune weight layout mismatch");
+  // the order of the slices above IS the flat layout; host_logic.h states the same layout as arithmetic (the CPU tests and the region table use it)
+  const tsthost::FullLayout fl = tsthost::full_layout(ctx->md);
+  if (fl.embed != ctx->embed - ctx->wb || fl.layer0 != ctx->layers[0].proj[P_QKV].W - ctx->wb || fl.lm_head != ctx->lm_head - ctx->wb ||
+      (gpt2 && fl.wpe != ctx->wpe - ctx->wb) || fl.tail != ctx->layers[0].attn_norm - ctx->wb)
+    return fail(ctx, TST_ESTATE, "internal: full fine-tune layout disagrees with host_logic.h full_layout");
+  if (!(ctx->kmajor & 1)) ALLOC(ctx->lm_headT, AT, (int64_t)V * d);
+  return TST_OK;
+}
+template <typename AT>
+int layer_weights(CtxT<AT>* ctx, LayerT<AT>& W) {
+  const int d = ctx->d;
+  if (ctx->parent) return TST_OK;
+  if (ctx->full) {
+    if (!(ctx->kmajor & 1))   // (else dX = dY . W on the NN member: one copy of every weight)
+      for (auto& P : W.proj) ALLOC(P.WT, AT, P.numel());
+    return TST_OK;
+  }
+  ALLOC(W.attn_norm, AT, d); ALLOC(W.mlp_norm, AT, d);
+  if (ctx->md.qkv_bias) ALLOC(W.bqkv, AT, ctx->dqkv);
+  if (ctx->qk_norm) { ALLOC(W.q_norm, AT, ctx->dh); ALLOC(W.k_norm, AT, ctx->dh); }
+  if (ctx->gpt2) {
+    ALLOC(W.attn_norm_b, AT, d); ALLOC(W.mlp_norm_b, AT, d);
+    ALLOC(W.bo, AT, d); ALLOC(W.bgu, AT, ctx->Fgu); ALLOC(W.bd, AT, d);
+  }
+  for (auto& P : W.proj) { ALLOC(P.W, AT, P.numel()); ALLOC(P.WT, AT, P.numel()); }
+  return TST_OK;
+}
+// the device side of one module group: its enabled modules and slot 0's offsets come from host_logic.h lora_layout, the other slots' follow once n1 is known (trainables)
+template <typename AT>
+int add_group(CtxT<AT>* ctx, LoraGroupT<AT>& g, const ProjT<AT>& P, const tsthost::LoraGroupLayout& lay) {
+  const int r = ctx->cfg.lora_r, din = P.din, dout = P.dout;
+  if (lay.nseg == 0) { g.on = false; return TST_OK; }
+  LoraGroupDescT<AT> dsc;
+  memset(&dsc, 0, sizeof(dsc));
+  for (int m = 0; m < lay.nseg; ++m) { dsc.seg_row0[m] = lay.row0[m]; dsc.seg_row1[m] = lay.row1[m]; dsc.a_off[m] = lay.a_off[m]; dsc.b_off[m] = lay.b_off[m]; }
+  dsc.din = din; dsc.dout = dout; dsc.r = r; dsc.nmod = lay.nseg; dsc.nslot = ctx->ns; dsc.nseg = lay.nseg * ctx->ns;
+  dsc.RP = roundup(dsc.nseg * r, 64);
+  dsc.scale = ctx->cfg.lora_alpha / (float)r;
+  ALLOC(dsc.Ag, AT, (int64_t)dsc.RP * din); ALLOC(dsc.AgT, AT, (int64_t)din * dsc.RP);
+  ALLOC(dsc.Bg, AT, (int64_t)dout * dsc.RP); ALLOC(dsc.BgT, AT, (int64_t)dsc.RP * dout);
+  ALLOC(dsc.dAg, float, (int64_t)dsc.RP * din); ALLOC(dsc.dBg, float, (int64_t)dout * dsc.RP);
+  g.on = true; g.d = dsc; g.index = (int)ctx->descs.size();
+  ctx->descs.push_back(dsc);
+  const long elems = (long)dsc.RP * din + (long)dout * dsc.RP;
+  if (elems > ctx->pack_max_elems) ctx->pack_max_elems = elems;
+  if (din > ctx->pack_max_long) ctx->pack_max_long = din;
+  if (dout > ctx->pack_max_long) ctx->pack_max_long = dout;
+  return TST_OK;
+}
+// per layer: its own weight allocations, its four module groups (LoRA; a full fine-tune has none), its stash
+template <typename AT>
+int build_layers(CtxT<AT>* ctx) {
+  const int d = ctx->d, F = ctx->F, Fgu = ctx->Fgu, T = ctx->Tpad_max;
+  tsthost::LoraLayout lay;
+  if (!ctx->full) {
+    lay = tsthost::lora_layout(ctx->md, ctx->cfg.lora_r, ctx->cfg.lora_targets, ctx->ns);
+    ctx->tinfo = lay.entries;
+    ctx->n_train = lay.n1;
+  }
+  for (int l = 0; l < ctx->L; ++l) {
+    LayerT<AT>& W = ctx->layers[l];
+    LoraGroupT<AT>* const groups[4] = {&W.g_qkv, &W.g_o, &W.g_gu, &W.g_d};
+    AT** const us[4] = {&W.us_qkv, &W.us_o, &W.us_gu, &W.us_d};
+    CTX_RC(layer_weights(ctx, W));
+    if (!ctx->full)
+      for (int p = 0; p < 4; ++p) CTX_RC(add_group(ctx, *groups[p], W.proj[p], lay.group[(size_t)4 * l + p]));
     // stash
     ALLOC(W.x_in, AT, (int64_t)T * d); ALLOC(W.xn1, AT, (int64_t)T * d); ALLOC(W.qkv, AT, (int64_t)T * ctx->dqkv);
     ALLOC(W.attn, AT, (int64_t)T * ctx->dattn); ALLOC(W.hmid, AT, (int64_t)T * d); ALLOC(W.xn2, AT, (int64_t)T * d);
     ALLOC(W.gu, AT, (int64_t)T * Fgu); ALLOC(W.act, AT, (int64_t)T * F);
     ALLOC(W.rstd1, float, 2 * T); ALLOC(W.rstd2, float, 2 * T); ALLOC(W.lse, float, (int64_t)ctx->H * T);  // LayerNorm keeps {mean, rstd}
-    if (qk_norm) { ALLOC(W.qk_raw, AT, (int64_t)T * (ctx->dq + ctx->dkv)); ALLOC(W.rstd_qk, float, (int64_t)T * (ctx->H + ctx->Hkv)); }
-    W.us_qkv = W.us_o = W.us_gu = W.us_d = nullptr;
-    if (W.g_qkv.on) ALLOC(W.us_qkv, AT, (int64_t)T * W.g_qkv.d.RP);
-    if (W.g_o.on) ALLOC(W.us_o, AT, (int64_t)T * W.g_o.d.RP);
-    if (W.g_gu.on) ALLOC(W.us_gu, AT, (int64_t)T * W.g_gu.d.RP);
-    if (W.g_d.on) ALLOC(W.us_d, AT, (int64_t)T * W.g_d.d.RP);
+    if (ctx->qk_norm) { ALLOC(W.qk_raw, AT, (int64_t)T * (ctx->dq + ctx->dkv)); ALLOC(W.rstd_qk, float, (int64_t)T * (ctx->H + ctx->Hkv)); }
+    for (int p = 0; p < 4; ++p) {
+      *us[p] = nullptr;
+      if (groups[p]->on) ALLOC(*us[p], AT, (int64_t)T * groups[p]->d.RP);
+    }
   }
   ALLOC(ctx->x_last, AT, (int64_t)T * d);
-  if (ctx->full) {
-    if (gpt2) ctx->lm_head = ctx->embed;  // tied head: one parameter, its gradient is the sum of both uses
-    else ctx->lm_head = take((int64_t)V * d);
-    // the no-decay tail, layer by layer: norm vectors and biases
-    for (auto& W : ctx->layers) {
-      if (gpt2) {
-        W.attn_norm = take(d); W.attn_norm_b = take(d); W.mlp_norm = take(d); W.mlp_norm_b = take(d);
-        W.bqkv = take(ctx->dqkv); W.bo = take(d); W.bgu = take(Fgu); W.bd = take(d);
-        continue;
-      }
-      W.attn_norm = take(d);
-      W.mlp_norm = take(d);
-      if (qkv_bias) W.bqkv = take(ctx->dqkv);
-      // Qwen3 head-norm vectors: with the other norm vectors in the no-decay tail (HF's Trainer excludes every "_norm" parameter from decay)
-      if (qk_norm) { W.q_norm = take(ctx->dh); W.k_norm = take(ctx->dh); }
-    }
-    ctx->final_norm = take(d);
-    if (gpt2) ctx->final_norm_b = take(d);
-    if (wofs != ctx->n_train) return fail(ctx, TST_ESTATE, "internal: full fine-tune weight layout mismatch");
-    {   // the allocation order above IS the flat layout; host_logic.h states the same layout as arithmetic (the CPU tests and the region table use it)
-      const tsthost::FullLayout fl = tsthost::full_layout(tsthost::model_dims(c));
-      if (fl.n_train != ctx->n_train || fl.n_decay != ctx->n_decay || fl.embed != ctx->embed - ctx->wb || fl.layer0 != ctx->layers[0].proj[P_QKV].W - ctx->wb ||
-          fl.lm_head != ctx->lm_head - ctx->wb || (gpt2 && fl.wpe != ctx->wpe - ctx->wb) || fl.tail != ctx->layers[0].attn_norm - ctx->wb)
-        return fail(ctx, TST_ESTATE, "internal: full fine-tune layout disagrees with host_logic.h full_layout");
-    }
-  }
-  if (ctx->n_train <= 0) return fail(ctx, TST_EINVAL, "no trainable parameters (lora_targets empty)");
+  return TST_OK;
+}
+// the flat trainable vector (ns slots of n1 elements) and its optimizer state
+template <typename AT>
+int trainables(CtxT<AT>* ctx) {
   ctx->n1 = ctx->n_train;
   ctx->n_train = ctx->n1 * ctx->ns;
   for (auto& g : ctx->descs)   // slot s keeps the layout of slot 0, shifted by s * n1
@@ -1760,26 +1705,31 @@ int build_ctx(CtxT<AT>* ctx) {
   ALLOC(ctx->descs_dev, LoraGroupDescT<AT>, ctx->descs.size());
   ALLOC(ctx->clip_out, float, 2 * TST_MAX_STACK); ALLOC(ctx->clip_partial, float, 4096);
   if (!ctx->d_loss) ALLOC(ctx->d_loss, float, TST_MAX_STACK);
-
-  // RoPE tables: inv_freq = theta^(-2i/dh) (modeling_llama.py:108), cos/sin cast to bf16 (:127)
-  if (sh) {
-    ctx->cosT = sh->cosT; ctx->sinT = sh->sinT;
-  } else if (!gpt2) {
-    const int half = ctx->dh / 2, P = c.max_position;
-    std::vector<float> hc((size_t)P * half), hs((size_t)P * half);
-    for (int i = 0; i < half; ++i) {
-      const float inv_freq = rope_inv_freq(c, i, ctx->dh);
-      for (int p = 0; p < P; ++p) {
-        const float ang = (float)p * inv_freq;
-        hc[(size_t)p * half + i] = sizeof(AT) == 2 ? host_bf2f(host_f2bf(cosf(ang))) : cosf(ang);
-        hs[(size_t)p * half + i] = sizeof(AT) == 2 ? host_bf2f(host_f2bf(sinf(ang))) : sinf(ang);
-      }
+  return TST_OK;
+}
+// RoPE tables: inv_freq = theta^(-2i/dh) (modeling_llama.py:108), cos/sin cast to bf16 (:127); a fork reads its parent's
+template <typename AT>
+int rope_tables(CtxT<AT>* ctx) {
+  const tst_model_cfg& c = ctx->cfg;
+  if (ctx->parent) { ctx->cosT = ctx->parent->cosT; ctx->sinT = ctx->parent->sinT; return TST_OK; }
+  if (ctx->gpt2) return TST_OK;
+  const int half = ctx->dh / 2, P = c.max_position;
+  std::vector<float> hc((size_t)P * half), hs((size_t)P * half);
+  for (int i = 0; i < half; ++i) {
+    const float inv_freq = rope_inv_freq(c, i, ctx->dh);
+    for (int p = 0; p < P; ++p) {
+      const float ang = (float)p * inv_freq;
+      hc[(size_t)p * half + i] = sizeof(AT) == 2 ? host_bf2f(host_f2bf(cosf(ang))) : cosf(ang);
+      hs[(size_t)p * half + i] = sizeof(AT) == 2 ? host_bf2f(host_f2bf(sinf(ang))) : sinf(ang);
     }
-    ALLOC(ctx->cosT, float, (int64_t)P * half); ALLOC(ctx->sinT, float, (int64_t)P * half);
-    CTX_HIP(hipMemcpy(ctx->cosT, hc.data(), hc.size() * 4, hipMemcpyHostToDevice));
-    CTX_HIP(hipMemcpy(ctx->sinT, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
   }
-  // batch buffers
+  ALLOC(ctx->cosT, float, (int64_t)P * half); ALLOC(ctx->sinT, float, (int64_t)P * half);
+  CTX_HIP(hipMemcpy(ctx->cosT, hc.data(), hc.size() * 4, hipMemcpyHostToDevice));
+  CTX_HIP(hipMemcpy(ctx->sinT, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
+  return TST_OK;
+}
+// the batch on the device (one int array, host_logic.h stage_ints) and the pinned buffers of the asynchronous entry points
+inline int batch_staging(tst_ctx* ctx) {
   const size_t stage_ints = tsthost::stage_ints(batch_limits(ctx));   // layout of upload_batch's staging buffer
   ALLOC(ctx->d_ids, int, stage_ints + 64);
   ctx->d_pos = ctx->d_ids + ctx->Tmax; ctx->d_cu = ctx->d_pos + ctx->Tmax; ctx->d_lab_idx = ctx->d_cu + (ctx->Smax + 1); ctx->d_targets = ctx->d_lab_idx + ctx->Rmax; ctx->d_order = ctx->d_targets + ctx->Rmax;
@@ -1796,23 +1746,28 @@ int build_ctx(CtxT<AT>* ctx) {
   CTX_HIP(hipHostMalloc((void**)&ctx->h_opt_ids, 256 * sizeof(int), hipHostMallocDefault));
   CTX_HIP(hipHostMalloc((void**)&ctx->h_metrics, 4 * TST_MAX_STACK * sizeof(float), hipHostMallocDefault));   // [loss of slot s (8) | {grad norm, clip coef} of slot s (16) | tst_fetch_loss (8)]
   memset(ctx->h_metrics, 0, 4 * TST_MAX_STACK * sizeof(float));
-  // head
-  const int R = roundup(ctx->Rmax, 64);  // whole 64-row k-steps are readable (lm_head dW contracts over the labelled rows)
+  return TST_OK;
+}
+
+template <typename AT>
+int head_workspace(CtxT<AT>* ctx) {
+  const int d = ctx->d, V = ctx->Vp, R = head_rows(ctx);
   ALLOC(ctx->xg, AT, (int64_t)R * d); ALLOC(ctx->xf, AT, (int64_t)R * d); ALLOC(ctx->dxf, AT, (int64_t)R * d); ALLOC(ctx->dxg, AT, (int64_t)R * d);
   ALLOC(ctx->dlogits, AT, (int64_t)R * V); ALLOC(ctx->rstd_f, float, 2 * R); ALLOC(ctx->logits, float, (int64_t)R * V);
   ALLOC(ctx->stats, float, (int64_t)R * 4); ALLOC(ctx->optl, float, (int64_t)R * 256);
-  // backward scratch
-  const int RPmax = 64;  // nseg*r <= 3*... ; groups are padded to multiples of 64, at most 3*64
-  int rp = RPmax;
-  for (auto& g : ctx->descs) if (g.RP > rp) rp = g.RP;
-  const int dout_max = (Fgu > ctx->dqkv) ? Fgu : ctx->dqkv;
-  const int din_max = (F > d) ? F : d;
+  return TST_OK;
+}
+// backward scratch. LoRA: the last layer's compact stash and one du buffer per module group for the side stream; full fine-tune: the gradient-norm slots,
+// the column-reduction workspaces and (without kmajor bit 1) the transposed activations of the weight-gradient contractions
+template <typename AT>
+int backward_scratch(CtxT<AT>* ctx) {
+  const int d = ctx->d, F = ctx->F, Fgu = ctx->Fgu, T = ctx->Tpad_max, R = head_rows(ctx), rp = rank_pad_max(ctx);
   ALLOC(ctx->dX, AT, (int64_t)T * d); ALLOC(ctx->dH, AT, (int64_t)T * d); ALLOC(ctx->dxn, AT, (int64_t)T * d);
   ALLOC(ctx->dattn_b, AT, (int64_t)T * ctx->dattn); ALLOC(ctx->dqkv_b, AT, (int64_t)T * ctx->dqkv);
   ALLOC(ctx->dact, AT, (int64_t)T * F); ALLOC(ctx->dgu, AT, (int64_t)T * Fgu);
   ALLOC(ctx->du, AT, (int64_t)T * rp);
   if (!ctx->full) {
-    static const bool lc_env = [] { const char* e = getenv("TST_LAST_COMPACT"); return !e || atoi(e) != 0; }();
+    static const bool lc_env = env_flag("TST_LAST_COMPACT", true);
     if (lc_env) {   // R = roundup64(Rmax) rows each: a few MB
       ALLOC(ctx->lc_attn, AT, (int64_t)R * ctx->dattn); ALLOC(ctx->lc_xin, AT, (int64_t)R * d); ALLOC(ctx->lc_hmid, AT, (int64_t)R * d);
       ALLOC(ctx->lc_xn2, AT, (int64_t)R * d); ALLOC(ctx->lc_gu, AT, (int64_t)R * Fgu); ALLOC(ctx->lc_act, AT, (int64_t)R * F);
@@ -1821,108 +1776,128 @@ int build_ctx(CtxT<AT>* ctx) {
       ALLOC(ctx->lc_dH, AT, (int64_t)R * d); ALLOC(ctx->lc_dattn, AT, (int64_t)R * ctx->dattn); ALLOC(ctx->lc_rstd2, float, 2 * (int64_t)R);
       ctx->lc_have = ctx->lc_on = true;
     }
-    static const bool no_side = [] { const char* e = getenv("TST_NO_SIDE_STREAM"); return e && atoi(e) != 0; }();
-    if (!no_side) {
+    if (wants_side_stream(ctx))
       for (int g = 0; g < 4; ++g) ALLOC(ctx->du4[g], AT, (int64_t)T * rp);
-      CTX_HIP(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-      CTX_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-      CTX_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-    }
-  }
-  if (ctx->full) {
+  } else {
     // gradient regions in the order backward finishes them: lm_head (untied), layers L-1 .. 0, embedding side, norm / bias tail (host_logic.h)
-    ctx->gn_regions = tsthost::full_layout(tsthost::model_dims(c)).regions;
-    for (int p = 0; p < 4; ++p) ctx->gn_cap += L * gn_slots(ctx->proj_dout[p], ctx->proj_din[p]);
+    ctx->gn_regions = tsthost::full_layout(ctx->md).regions;
+    for (int p = 0; p < 4; ++p) ctx->gn_cap += ctx->L * gn_slots(ctx->proj_dout[p], ctx->proj_din[p]);
     ctx->gn_cap += 3 * 1024;   // embedding side, head, norm / bias tail: summed at the optimizer step
     ALLOC(ctx->gn_partial, float, ctx->gn_cap);
-  }
-  if (ctx->full) {   // the weight-gradient contractions run beside the dX chain (linear_bwd)
-    // TST_DW_CUS=n (A/B switch): the weight gradients' stream confined to n CUs, as the optimizer's below -- the dX chain and the small kernels between its
-    // contractions then always find free CUs
-    static const int dw_cus = [] { const char* e = getenv("TST_DW_CUS"); return e ? atoi(e) : 0; }();
-    hipDeviceProp_t prop;
-    if (dw_cus > 0 && dw_cus < 256 && hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount == 256) {
-      ctx->side = masked_stream(ctx->device, dw_cus);
-      if (!ctx->side) return fail(ctx, TST_EHIP, "hipExtStreamCreateWithCUMask failed");
-      ctx->side_shared = true;
-    } else
-    CTX_HIP(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-    CTX_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    CTX_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-  }
-  if (ctx->full && !ctx->zero_on) {
-    // the optimizer's own stream (see tst_ctx::opt_stream), confined to 192 of the 256 CUs (TST_OPT_CUS = n; 0 = a plain stream), the same share of every
-    // XCD (the driver deals the mask's bits round-robin over the XCDs, then over an XCD's shader engines): a 256-VGPR, 128 KB-LDS projection tile needs an
-    // EMPTY CU, and AdamW blocks streaming over all CUs keep the next forward's tiles waiting for one. A CU streams at most ~37 GB/s, so AdamW needs most of
-    // the chip for the HBM rate; 192 measured best (profiles/r04_full_overlap_ab.txt block 8: 21.13 -> 21.51 QA-pairs/s; 176 / 208: +0.6 / +0.5 %).
-    static const int opt_cus_env = [] { const char* e = getenv("TST_OPT_CUS"); return e ? atoi(e) : 160; }();
-    int opt_cus = opt_cus_env;
-    {
-      hipDeviceProp_t prop;
-      if (hipGetDeviceProperties(&prop, ctx->device) != hipSuccess || prop.multiProcessorCount != 256) opt_cus = 0;   // (another partition mode: no mask)
-    }
-    if (opt_cus > 0 && opt_cus < 256) {
-      ctx->opt_stream = masked_stream(ctx->device, opt_cus);
-      if (!ctx->opt_stream) return fail(ctx, TST_EHIP, "hipExtStreamCreateWithCUMask failed");
-      ctx->opt_stream_shared = true;
-    } else {
-      // TST_OPT_PRIO=1: the optimizer's queue at the device's LOWEST priority -- the forward's workgroups are dispatched first, AdamW takes what is left
-      static const bool low = env_flag("TST_OPT_PRIO", false);
-      int lo = 0, hi = 0;
-      if (low && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) CTX_HIP(hipStreamCreateWithPriority(&ctx->opt_stream, hipStreamNonBlocking, lo));
-      else CTX_HIP(hipStreamCreateWithFlags(&ctx->opt_stream, hipStreamNonBlocking));
-    }
-    CTX_HIP(hipEventCreateWithFlags(&ctx->opt_go, hipEventDisableTiming));
-    ctx->opt_ev.resize((size_t)L + 2);
-    for (auto& e : ctx->opt_ev) CTX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  if (ctx->full) {   // transposed activations for the weight-gradient contractions
+    const int dout_max = (Fgu > ctx->dqkv) ? Fgu : ctx->dqkv, din_max = (F > d) ? F : d;
     ALLOC(ctx->colred_ws, float, 2 * colred_ws_floats(T, dout_max > d ? dout_max : d));
     ALLOC(ctx->colred_ws_side, float, 2 * colred_ws_floats(T, d));
-    if (qk_norm) ALLOC(ctx->hn_ws, float, HEAD_NORM_WS_FLOATS);
-    for (auto& e : ctx->ev_ndw) CTX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (!(ctx->kmajor & 2)) {   // (else dW = dy^T . x on the TN member: no transposed copies)
+    if (ctx->qk_norm) ALLOC(ctx->hn_ws, float, HEAD_NORM_WS_FLOATS);
+    if (!(ctx->kmajor & 2)) {   // transposed activations for the weight-gradient contractions (else dW = dy^T . x on the TN member: no transposed copies)
       ALLOC(ctx->dyT, AT, (int64_t)dout_max * T);
       ALLOC(ctx->xT, AT, (int64_t)din_max * T);
     }
   }
-  (void)dout_max; (void)din_max; (void)Tp;
   ALLOC(ctx->delta, float, (int64_t)ctx->H * T);
-  // split-K slabs: sized for the largest planned split of any shape this engine issues
-  {
-    size_t need = 64u << 20;
-    auto consider = [&](int M, int N, int K, int K2) {
-      int v, sk;
-      gemm_plan(M, N, K, K2, &v, &sk);
-      const size_t b = gemm_slab_bytes(M, N, sk);
-      if (b > need) need = b;
-      const size_t b2 = (long)tst_ceil_div(M, 256) * tst_ceil_div(N, 256) <= 128 ? gemm_slab_bytes(M, N, 4) : 0;   // tile policy 3 may be switched on later
-      if (b2 > need) need = b2;
-    };
-    consider(T, ctx->dqkv, d, rp); consider(T, d, ctx->dattn, rp); consider(T, Fgu, d, rp); consider(T, d, F, rp);
-    consider(T, d, ctx->dqkv, rp); consider(T, ctx->dattn, d, rp); consider(T, d, Fgu, rp); consider(T, F, d, rp);
-    consider(T, rp, d, 0); consider(T, rp, F, 0); consider(T, rp, Fgu, 0); consider(T, rp, ctx->dqkv, 0);
-    consider(Fgu, rp, Tp, 0); consider(ctx->dqkv, rp, Tp, 0); consider(d, rp, Tp, 0);
-    consider(rp, d, Tp, 0); consider(rp, F, Tp, 0);
-    consider(R, V, d, 0); consider(R, d, V, 0);
-    ctx->slab_bytes = need;
-    ctx->slab = (float*)ctx->pool.alloc((int64_t)need);
-    if (!ctx->slab) return fail(ctx, TST_ENOMEM, "hipMalloc failed: slab");
-    if (ctx->side) {   // the side stream's split-K contractions (LoRA: token axis, <= 64 columns on one side; full fine-tune: the weight gradients' tail slices) need their own slabs
-      ctx->side_slab_bytes = ctx->full ? need : (64u << 20);
-      ctx->side_slab = (float*)ctx->pool.alloc((int64_t)ctx->side_slab_bytes);
-      if (!ctx->side_slab) return fail(ctx, TST_ENOMEM, "hipMalloc failed: side slab");
+  return TST_OK;
+}
+// The streams beside the context's own. side: LoRA's adapter-gradient contractions, a full fine-tune's weight-gradient contractions (linear_bwd).
+// opt_stream: the optimizer of an unsharded full fine-tune (see tst_ctx::opt_stream).
+inline int make_streams(tst_ctx* ctx) {
+  int cus = 0;   // a CU mask is laid out for the 256 CUs of the unpartitioned device (another partition mode: no mask)
+  hipDeviceProp_t prop;
+  if (ctx->full && hipGetDeviceProperties(&prop, ctx->device) == hipSuccess) cus = prop.multiProcessorCount;
+  if (wants_side_stream(ctx)) {
+    // TST_DW_CUS=n (A/B switch, full fine-tune): the weight gradients' stream confined to n CUs, as the optimizer's below -- the dX chain and the small kernels
+    // between its contractions then always find free CUs
+    int dw_cus = 0;
+    if (ctx->full) { static const int dw_cus_env = env_int("TST_DW_CUS", 0); dw_cus = dw_cus_env; }
+    if (dw_cus > 0 && dw_cus < 256 && cus == 256) {
+      ctx->side = masked_stream(ctx->device, dw_cus);
+      if (!ctx->side) return fail(ctx, TST_EHIP, "hipExtStreamCreateWithCUMask failed");
+      ctx->side_shared = true;
+    } else {
+      CTX_HIP(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
     }
+    CTX_HIP(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+    CTX_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
   }
-#undef ALLOC
-  if (gpt2) name_tensors_gpt2(ctx);
+  if (ctx->full)
+    for (auto& e : ctx->ev_ndw) CTX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  if (!ctx->full || ctx->zero_on) return TST_OK;
+  // The optimizer's stream is confined to 160 of the 256 CUs (TST_OPT_CUS = n; 0 = a plain stream), the same share of every XCD (the driver deals the
+  // mask's bits round-robin over the XCDs, then over an XCD's shader engines): a 256-VGPR, 128 KB-LDS projection tile needs an EMPTY CU, and AdamW blocks
+  // streaming over all CUs keep the next forward's tiles waiting for one. A CU streams at most ~37 GB/s, so AdamW needs most of the chip for the HBM rate.
+  // 160 measured best (profiles/r05_full_opt_cus_ab.txt: 23.74 QA-pairs/s against 22.94 / 23.47 / 23.30 / 22.82 / 22.52 at 128 / 152 / 168 / 192 / 208;
+  // DESIGN.md section 8). Round 4 had settled on 192 (profiles/r04_full_overlap_ab.txt block 8; docs/DESIGN_HISTORY.md).
+  static const int opt_cus = env_int("TST_OPT_CUS", 160);
+  if (opt_cus > 0 && opt_cus < 256 && cus == 256) {
+    ctx->opt_stream = masked_stream(ctx->device, opt_cus);
+    if (!ctx->opt_stream) return fail(ctx, TST_EHIP, "hipExtStreamCreateWithCUMask failed");
+    ctx->opt_stream_shared = true;
+  } else {
+    // TST_OPT_PRIO=1: the optimizer's queue at the device's LOWEST priority -- the forward's workgroups are dispatched first, AdamW takes what is left
+    static const bool low = env_flag("TST_OPT_PRIO", false);
+    int lo = 0, hi = 0;
+    if (low && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) CTX_HIP(hipStreamCreateWithPriority(&ctx->opt_stream, hipStreamNonBlocking, lo));
+    else CTX_HIP(hipStreamCreateWithFlags(&ctx->opt_stream, hipStreamNonBlocking));
+  }
+  CTX_HIP(hipEventCreateWithFlags(&ctx->opt_go, hipEventDisableTiming));
+  ctx->opt_ev.resize((size_t)ctx->L + 2);
+  for (auto& e : ctx->opt_ev) CTX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return TST_OK;
+}
+// split-K slabs: sized for the largest planned split of any shape this engine issues
+template <typename AT>
+int splitk_slabs(CtxT<AT>* ctx) {
+  const int d = ctx->d, F = ctx->F, Fgu = ctx->Fgu, V = ctx->Vp, T = ctx->Tpad_max, R = head_rows(ctx), rp = rank_pad_max(ctx);
+  size_t need = 64u << 20;
+  auto consider = [&](int M, int N, int K, int K2) {
+    int v, sk;
+    gemm_plan(M, N, K, K2, &v, &sk);
+    const size_t b = gemm_slab_bytes(M, N, sk);
+    if (b > need) need = b;
+    const size_t b2 = (long)tst_ceil_div(M, 256) * tst_ceil_div(N, 256) <= 128 ? gemm_slab_bytes(M, N, 4) : 0;   // tile policy 3 may be switched on later
+    if (b2 > need) need = b2;
+  };
+  consider(T, ctx->dqkv, d, rp); consider(T, d, ctx->dattn, rp); consider(T, Fgu, d, rp); consider(T, d, F, rp);
+  consider(T, d, ctx->dqkv, rp); consider(T, ctx->dattn, d, rp); consider(T, d, Fgu, rp); consider(T, F, d, rp);
+  consider(T, rp, d, 0); consider(T, rp, F, 0); consider(T, rp, Fgu, 0); consider(T, rp, ctx->dqkv, 0);
+  consider(Fgu, rp, T, 0); consider(ctx->dqkv, rp, T, 0); consider(d, rp, T, 0);
+  consider(rp, d, T, 0); consider(rp, F, T, 0);
+  consider(R, V, d, 0); consider(R, d, V, 0);
+  ctx->slab_bytes = need;
+  ctx->slab = (float*)ctx->pool.alloc((int64_t)need);
+  if (!ctx->slab) return fail(ctx, TST_ENOMEM, "hipMalloc failed: slab");
+  if (ctx->side) {   // the side stream's split-K contractions (LoRA: token axis, <= 64 columns on one side; full fine-tune: the weight gradients' tail slices) need their own slabs
+    ctx->side_slab_bytes = ctx->full ? need : (64u << 20);
+    ctx->side_slab = (float*)ctx->pool.alloc((int64_t)ctx->side_slab_bytes);
+    if (!ctx->side_slab) return fail(ctx, TST_ENOMEM, "hipMalloc failed: side slab");
+  }
+  return TST_OK;
+}
+// the state_dict name table; the trainables of a full fine-tune are its entries inside the flat buffer, in its order (a LoRA context's are the module groups')
+template <typename AT>
+int name_tables(CtxT<AT>* ctx) {
+  if (ctx->gpt2) name_tensors_gpt2(ctx);
   else name_tensors_llama(ctx);
-  if (ctx->full) {
-    // the trainables of a full fine-tune: the named tensors inside the flat buffer, in its order (tinfo is empty so far: no module group exists)
-    for (const auto& t : ctx->named)
-      if (!t.alias && t.ptr >= ctx->wb && t.ptr < ctx->wb + ctx->n_train) ctx->tinfo.push_back({t.name, (int64_t)(t.ptr - ctx->wb), t.rows, t.cols});
-    std::sort(ctx->tinfo.begin(), ctx->tinfo.end(), [](const TrainableInfo& a, const TrainableInfo& b) { return a.offset < b.offset; });
-  }
+  if (!ctx->full) return TST_OK;
+  for (const auto& t : ctx->named)
+    if (!t.alias && t.ptr >= ctx->wb && t.ptr < ctx->wb + ctx->n_train) ctx->tinfo.push_back({t.name, (int64_t)(t.ptr - ctx->wb), t.rows, t.cols});
+  std::sort(ctx->tinfo.begin(), ctx->tinfo.end(), [](const TrainableInfo& a, const TrainableInfo& b) { return a.offset < b.offset; });
+  return TST_OK;
+}
+#undef ALLOC
+
+template <typename AT>
+int build_ctx(CtxT<AT>* ctx) {
+  // (no configuration check here: tst_create and fork_impl, the two callers, have run host_logic.h check_cfg before they allocated the context)
+  CTX_RC(set_dims(ctx));
+  CTX_RC(weight_storage(ctx));
+  CTX_RC(build_layers(ctx));
+  CTX_RC(trainables(ctx));
+  CTX_RC(rope_tables(ctx));
+  CTX_RC(batch_staging(ctx));
+  CTX_RC(head_workspace(ctx));
+  CTX_RC(backward_scratch(ctx));
+  CTX_RC(make_streams(ctx));
+  CTX_RC(splitk_slabs(ctx));
+  CTX_RC(name_tables(ctx));
   CTX_HIP(hipMemcpy(ctx->descs_dev, ctx->descs.data(), ctx->descs.size() * sizeof(LoraGroupDescT<AT>), hipMemcpyHostToDevice));
   CTX_HIP(hipDeviceSynchronize());  // the ctx stream is non-blocking: setup copies/memsets must have landed before it is used
   return TST_OK;
@@ -1937,6 +1912,7 @@ template <typename AT>
 int fork_impl(CtxT<AT>* parent, tst_ctx** out) {
   if (parent->parent) return fail(parent, TST_EINVAL, "fork from the root context, not from a fork");
   if (!parent->finalized) return fail(parent, TST_ESTATE, "finalise the parent's weights before forking");
+  if (const int rc = tsthost::check_cfg(parent->cfg, true, parent->err)) return rc;   // (a full fine-tune cannot be forked)
   if (hipSetDevice(parent->device) != hipSuccess) return fail(parent, TST_EHIP, "hipSetDevice failed");
   CtxT<AT>* ctx = new CtxT<AT>();
   ctx->cfg = parent->cfg;
@@ -2269,7 +2245,7 @@ int opt_enqueue(CtxT<AT>* ctx, float lr, float* tg) {
   if (ctx->full && ctx->gn_fused && ctx->gn_used + 3 * 1024 <= ctx->gn_cap) {
     // the layer matrices' sums of squares are in their slots; what is left: everything outside the per-layer regions
     const int64_t first = ctx->layers[0].proj[P_QKV].W - ctx->wb;
-    const int64_t after = first + ctx->L * layer_numel(ctx);
+    const int64_t after = first + ctx->L * ctx->per_layer;
     float* rest = ctx->gn_partial + ctx->gn_used;
     // (1024 / 2048 workgroups: 256 pulled the 2.1 GB of the embedding gradient at 2.3 TB/s)
     CTX_RC(sumsq_partial(st, tg, first, rest, 1024));                                  // embedding side
@@ -2840,7 +2816,7 @@ int tst_create(const tst_model_cfg* cfg, int device, tst_ctx** out) {
     g_create_err = std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only";
     return TST_EHIP;
   }
-  if (cfg->precision != TST_PRECISION_BF16 && cfg->precision != TST_PRECISION_STRICT) { g_create_err = "precision must be TST_PRECISION_BF16 or TST_PRECISION_STRICT"; return TST_EINVAL; }
+  if (const int rc = tsthost::check_cfg(*cfg, false, g_create_err)) return rc;   // (before anything is allocated; the precision decides the context's type)
   const bool strict = cfg->precision == TST_PRECISION_STRICT;
   tst_ctx* ctx = strict ? static_cast<tst_ctx*>(new CtxT<float>()) : static_cast<tst_ctx*>(new CtxT<bf16_t>());
   ctx->cfg = *cfg;

@@ -31,6 +31,32 @@ int tst_host_full_layout(const tst_model_cfg* cfg, int64_t* out8, int64_t* regio
   return TST_OK;
 }
 
+int tst_host_check_cfg(const tst_model_cfg* cfg, int is_fork, char* err_out, int err_cap) {
+  if (!cfg) return TST_EINVAL;
+  std::string err;
+  const int rc = tsthost::check_cfg(*cfg, is_fork != 0, err);
+  if (err_out && err_cap > 0) {
+    strncpy(err_out, err.c_str(), (size_t)err_cap - 1);
+    err_out[err_cap - 1] = 0;
+  }
+  return rc;
+}
+
+int tst_host_lora_layout(const tst_model_cfg* cfg, int64_t* out3, char* names_out, int name_cap, int64_t* entries_out, int cap) {
+  if (!cfg || !out3 || cfg->num_layers < 0 || cfg->lora_r < 0) return TST_EINVAL;
+  const tsthost::LoraLayout l = tsthost::lora_layout(tsthost::model_dims(*cfg), cfg->lora_r, cfg->lora_targets, cfg->n_stack);
+  out3[0] = l.n1; out3[1] = l.n_train; out3[2] = (int64_t)l.entries.size();
+  for (int i = 0; i < (int)l.entries.size() && i < cap; ++i) {
+    const tsthost::TrainableEntry& e = l.entries[(size_t)i];
+    if (names_out && name_cap > 0) {
+      strncpy(names_out + (size_t)i * name_cap, e.name.c_str(), (size_t)name_cap - 1);
+      names_out[(size_t)i * name_cap + name_cap - 1] = 0;
+    }
+    if (entries_out) { entries_out[3 * i] = e.offset; entries_out[3 * i + 1] = e.rows; entries_out[3 * i + 2] = e.cols; }
+  }
+  return TST_OK;
+}
+
 static tsthost::BatchLimits limits_of(const tst_model_cfg& c) {
   return {c.max_tokens, c.max_seqs, c.max_labelled, c.vocab_size, c.max_position, c.n_stack > 1 ? c.n_stack : 1};
 }

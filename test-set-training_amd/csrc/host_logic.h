@@ -1,7 +1,8 @@
-// Host-only arithmetic of the engine -- batch validation and the labelled-row map, the flat layout of a full fine-tune and its gradient regions,
-// the ZeRO-1 shard map, the RoPE inverse frequencies. No HIP type appears here: the same header is compiled into libtst_hip.so by hipcc (engine.hip
-// calls these functions on the product path) and, by g++ with -fsanitize=address,undefined, into the self-test csrc/host_selftest.cpp and the CPU-only
-// library libtst_host.so (include/tst_host.h) that the CPU tests drive (SURVEY.md section 5 "sanitizers": run on the CPU build only).
+// Host-only arithmetic of the engine -- validation of the configuration and of every batch, the labelled-row map, the flat layout of a full fine-tune and
+// its gradient regions, the trainable table of the LoRA module groups, the ZeRO-1 shard map, the RoPE inverse frequencies. No HIP type appears here: the
+// same header is compiled into libtst_hip.so by hipcc (engine.hip calls these functions on the product path) and, by g++ with
+// -fsanitize=address,undefined, into the self-test csrc/host_selftest.cpp and the CPU-only library libtst_host.so (include/tst_host.h) that the CPU
+// tests drive (SURVEY.md section 5 "sanitizers": run on the CPU build only).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -87,6 +88,11 @@ inline ModelDims model_dims(const tst_model_cfg& c) {
   m.dq = c.num_heads * c.head_dim; m.dkv = c.num_kv_heads * c.head_dim; m.dqkv = m.dq + 2 * m.dkv; m.dattn = m.dq;
   return m;
 }
+// a layer's four projections [dout, din]: q|k|v, o, gate|up (GPT-2: c_fc), down -- the order of the flat buffer, the optimizer and the module groups
+inline void proj_dims(const ModelDims& m, int dout[4], int din[4]) {
+  const int pd[4][2] = {{m.dqkv, m.d}, {m.d, m.dattn}, {m.Fgu, m.d}, {m.d, m.F}};
+  for (int p = 0; p < 4; ++p) { dout[p] = pd[p][0]; din[p] = pd[p][1]; }
+}
 struct FullLayout {
   int64_t n_decay = 0, n_train = 0, per_layer = 0;
   int64_t embed = 0, wpe = -1, lm_head = -1, layer0 = 0;   // offsets (lm_head = embed when tied)
@@ -110,6 +116,87 @@ inline FullLayout full_layout(const ModelDims& m) {
   f.regions.push_back({0, f.layer0});
   f.regions.push_back({f.tail, f.n_train - f.tail});
   return f;
+}
+
+// ------------------------------------------------------------------------------------------------ the configuration: what tst_create / tst_fork refuse
+// Every refusal the engine makes from the tst_model_cfg alone, BEFORE anything is allocated; TST_OK, or TST_EINVAL with `err` set. is_fork: the configuration
+// of a context about to be forked (tst_fork). The order is part of the interface: a configuration with several faults reports the first.
+inline int check_cfg(const tst_model_cfg& c, bool is_fork, std::string& err) {
+  auto fail = [&](const char* m) { err = m; return TST_EINVAL; };
+  if (c.precision != TST_PRECISION_BF16 && c.precision != TST_PRECISION_STRICT) return fail("precision must be TST_PRECISION_BF16 or TST_PRECISION_STRICT");
+  const bool gpt2 = c.arch == TST_ARCH_GPT2, full = c.train_mode == TST_TRAIN_FULL;
+  if (c.arch != TST_ARCH_LLAMA && c.arch != TST_ARCH_QWEN2 && c.arch != TST_ARCH_QWEN3 && !gpt2) return fail("unsupported arch");
+  if (c.hidden_size <= 0 || c.num_layers <= 0 || c.num_heads <= 0 || c.num_kv_heads <= 0 || c.head_dim <= 0 || c.intermediate_size <= 0 || c.vocab_size <= 0)
+    return fail("hidden_size/num_layers/num_heads/num_kv_heads/head_dim/intermediate_size/vocab_size must be > 0");
+  const ModelDims m = model_dims(c);
+  if (gpt2 && c.num_kv_heads != c.num_heads) return fail("GPT-2: num_kv_heads must equal num_heads");
+  if (gpt2 && m.dq != m.d) return fail("GPT-2: num_heads * head_dim must equal hidden_size");
+  if (c.train_mode != TST_TRAIN_LORA && !full) return fail("train_mode must be TST_TRAIN_LORA or TST_TRAIN_FULL");
+  if (full && is_fork) return fail("full fine-tune contexts cannot be forked (every fold owns its weights)");
+  if (m.dh != 128 && !(gpt2 && m.dh == 64)) return fail("head_dim must be 128 (GPT-2 family: 64 or 128)");
+  if (m.d % 64 || m.F % 64 || m.dq % 64 || m.dkv % 64) return fail("hidden/intermediate/head sizes must be multiples of 64");
+  if (c.num_heads % c.num_kv_heads) return fail("num_heads must be a multiple of num_kv_heads");
+  if (c.max_tokens <= 0 || c.max_seqs <= 0 || c.max_labelled <= 0 || c.max_position <= 0) return fail("max_tokens/max_seqs/max_labelled/max_position must be > 0");
+  if (!full && (c.lora_r <= 0 || c.lora_r > 64 || (64 % c.lora_r) != 0)) return fail("lora_r must divide 64");
+  if (!gpt2 && c.rope_scaling != TST_ROPE_DEFAULT) {
+    if (c.rope_scaling != TST_ROPE_LINEAR && c.rope_scaling != TST_ROPE_LLAMA3) return fail("rope_scaling must be TST_ROPE_DEFAULT, TST_ROPE_LINEAR or TST_ROPE_LLAMA3");
+    if (!(c.rope_factor > 0.f)) return fail("rope_factor must be > 0");
+    if (c.rope_scaling == TST_ROPE_LLAMA3 && (!(c.rope_low_freq_factor > 0.f) || !(c.rope_high_freq_factor > c.rope_low_freq_factor) || c.rope_original_max_position <= 0))
+      return fail("llama3 rope scaling needs 0 < rope_low_freq_factor < rope_high_freq_factor and rope_original_max_position > 0");
+  }
+  const bool stacked = c.n_stack > 1, zero_on = c.zero_ranks >= 1;
+  if (c.n_stack > kMaxStack) return fail("n_stack must be <= 8");
+  if (stacked && full) return fail("stacked folds need frozen base weights (LoRA): a full fine-tune owns its weights");
+  if (stacked && (c.lora_r & 7)) return fail("stacked folds: lora_r must be a multiple of 8");
+  if (stacked && c.precision == TST_PRECISION_STRICT) return fail("stacked folds are a bf16-path feature: precision = strict runs one fold per context");
+  if (zero_on && !full) return fail("optimizer-state sharding (zero_ranks >= 1) is for full fine-tunes: LoRA state is 0.2 % of the model");
+  if (zero_on && (c.zero_rank < 0 || c.zero_rank >= c.zero_ranks || c.zero_ranks > 64)) return fail("zero_rank must be in [0, zero_ranks), zero_ranks <= 64");
+  if (!full && !(c.lora_targets & TST_LORA_ALL)) return fail("no trainable parameters (lora_targets empty)");   // (both families' tables below cover every bit)
+  return TST_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ LoRA module groups and their trainable table
+// A layer has one module group per projection (P_QKV .. P_D, proj_dims' order): the peft modules that share the projection's input, each owning a row range of
+// its output. Per naming family: the modules of the four groups and the target bit(s) that enable each; module j's rows end at split[j], the last one's at dout.
+// GPT-2's peft targets are its four Conv1D modules: c_attn (any of Q/K/V), attn.c_proj (O), c_fc (GATE/UP), mlp.c_proj (DOWN).
+struct LoraModule { const char* name; unsigned bits; };
+struct LoraGroupSpec { int nmod; LoraModule mod[3]; };
+constexpr LoraGroupSpec kLoraLlama[4] = {{3, {{"q_proj", TST_LORA_Q}, {"k_proj", TST_LORA_K}, {"v_proj", TST_LORA_V}}}, {1, {{"o_proj", TST_LORA_O}}},
+                                         {2, {{"gate_proj", TST_LORA_GATE}, {"up_proj", TST_LORA_UP}}}, {1, {{"down_proj", TST_LORA_DOWN}}}};
+constexpr LoraGroupSpec kLoraGpt2[4] = {{1, {{"attn.c_attn", TST_LORA_Q | TST_LORA_K | TST_LORA_V}}}, {1, {{"attn.c_proj", TST_LORA_O}}},
+                                        {1, {{"mlp.c_fc", TST_LORA_GATE | TST_LORA_UP}}}, {1, {{"mlp.c_proj", TST_LORA_DOWN}}}};
+// The flat trainable vector of ONE slot: per layer, per group, per enabled module lora_A [r, din] then lora_B [rows, r]; slot s of a stacked context holds the
+// same table shifted by s * n1. group[4 l + p] = the enabled modules of layer l's projection p: their row ranges and the offsets of A and B.
+struct TrainableEntry { std::string name; int64_t offset, rows, cols; };
+struct LoraGroupLayout { int nseg = 0, row0[3], row1[3]; int64_t a_off[3], b_off[3]; };
+struct LoraLayout { int64_t n1 = 0, n_train = 0; std::vector<TrainableEntry> entries; std::vector<LoraGroupLayout> group; };
+inline LoraLayout lora_layout(const ModelDims& m, int r, unsigned targets, int n_stack) {
+  LoraLayout out;
+  int dout[4], din[4];
+  proj_dims(m, dout, din);
+  const int split[4][2] = {{m.dq, m.dq + m.dkv}, {0, 0}, {m.F, 0}, {0, 0}};
+  out.group.resize((size_t)(m.L > 0 ? m.L : 0) * 4);
+  for (int l = 0; l < m.L; ++l)
+    for (int p = 0; p < 4; ++p) {
+      const LoraGroupSpec& spec = (m.gpt2 ? kLoraGpt2 : kLoraLlama)[p];
+      LoraGroupLayout& g = out.group[(size_t)4 * l + p];
+      for (int j = 0, row = 0; j < spec.nmod; ++j) {
+        const int end = j + 1 < spec.nmod ? split[p][j] : dout[p];
+        if (targets & spec.mod[j].bits) {
+          const std::string pre = "layers." + std::to_string(l) + "." + spec.mod[j].name;
+          g.row0[g.nseg] = row; g.row1[g.nseg] = end;
+          g.a_off[g.nseg] = out.n1;
+          out.entries.push_back({pre + ".lora_A", out.n1, r, din[p]});
+          out.n1 += (int64_t)r * din[p];
+          g.b_off[g.nseg++] = out.n1;
+          out.entries.push_back({pre + ".lora_B", out.n1, end - row, r});
+          out.n1 += (int64_t)(end - row) * r;
+        }
+        row = end;
+      }
+    }
+  out.n_train = out.n1 * (n_stack > 1 ? n_stack : 1);
+  return out;
 }
 
 // ------------------------------------------------------------------------------------------------ batch validation + the labelled-row map

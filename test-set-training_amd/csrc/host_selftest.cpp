@@ -381,12 +381,165 @@ static void test_ig() {
   CHECK(trim_tokens_i32(base, cu1, cu1, 0, dst.get()) == TST_OK);
 }
 
+// one valid configuration per naming family and train mode (the tiny shapes of tests/golden_inputs.py)
+static tst_model_cfg valid_cfg(int arch, int train_mode) {
+  tst_model_cfg c;
+  memset(&c, 0, sizeof(c));
+  c.arch = arch; c.vocab_size = 256; c.hidden_size = 256; c.num_layers = 2; c.num_heads = 2; c.num_kv_heads = 1; c.head_dim = 128; c.intermediate_size = 256;
+  if (arch == TST_ARCH_GPT2) { c.vocab_size = 1001; c.hidden_size = 128; c.num_kv_heads = 2; c.head_dim = 64; c.intermediate_size = 512; }
+  c.rope_theta = 10000.0f; c.rms_norm_eps = 1e-5f; c.max_position = 128; c.max_tokens = 256; c.max_seqs = 8; c.max_labelled = 32;
+  c.train_mode = train_mode; c.lora_r = 16; c.lora_alpha = 32.0f; c.lora_targets = TST_LORA_ALL; c.n_stack = 1; c.precision = TST_PRECISION_BF16;
+  return c;
+}
+
+// check_cfg: every refusal tst_create / tst_fork make from the configuration, each on a configuration that differs from a valid one in ONE field
+static void test_check_cfg() {
+  std::string err;
+  for (int arch : {TST_ARCH_LLAMA, TST_ARCH_QWEN2, TST_ARCH_GPT2, TST_ARCH_QWEN3})
+    for (int mode : {TST_TRAIN_LORA, TST_TRAIN_FULL}) {
+      tst_model_cfg c = valid_cfg(arch, mode);
+      err = "stale";
+      CHECK(check_cfg(c, false, err) == TST_OK);
+      CHECK(check_cfg(c, mode == TST_TRAIN_LORA, err) == TST_OK);   // (a LoRA context may be forked)
+      c.precision = TST_PRECISION_STRICT;
+      CHECK(check_cfg(c, false, err) == TST_OK);
+      if (mode == TST_TRAIN_LORA) { c.precision = TST_PRECISION_BF16; c.n_stack = kMaxStack; CHECK(check_cfg(c, false, err) == TST_OK); }
+      if (mode == TST_TRAIN_FULL) { c.zero_ranks = 64; c.zero_rank = 63; CHECK(check_cfg(c, false, err) == TST_OK); }
+    }
+  const tst_model_cfg lora = valid_cfg(TST_ARCH_LLAMA, TST_TRAIN_LORA), full = valid_cfg(TST_ARCH_LLAMA, TST_TRAIN_FULL), gpt2 = valid_cfg(TST_ARCH_GPT2, TST_TRAIN_LORA);
+  tst_model_cfg linear = lora; linear.rope_scaling = TST_ROPE_LINEAR; linear.rope_factor = 4.0f;
+  tst_model_cfg l3 = lora; l3.rope_scaling = TST_ROPE_LLAMA3; l3.rope_factor = 8.0f; l3.rope_low_freq_factor = 1.0f; l3.rope_high_freq_factor = 4.0f; l3.rope_original_max_position = 64;
+  tst_model_cfg r4 = lora; r4.lora_r = 4;
+  tst_model_cfg strict = lora; strict.precision = TST_PRECISION_STRICT;
+  CHECK(check_cfg(linear, false, err) == TST_OK && check_cfg(l3, false, err) == TST_OK && check_cfg(r4, false, err) == TST_OK);
+  int n = 0;
+  auto refused = [&](tst_model_cfg c, const char* msg, bool is_fork = false) {
+    err.clear();
+    const int rc = check_cfg(c, is_fork, err);
+    if (rc != TST_EINVAL || err != msg) { fprintf(stderr, "refusal %d: rc=%d \"%s\", expected \"%s\"\n", n, rc, err.c_str(), msg); ++g_fail; }
+    ++n;
+  };
+#define WITH(base, stmt) [&] { tst_model_cfg c = base; stmt; return c; }()
+  const char* positive = "hidden_size/num_layers/num_heads/num_kv_heads/head_dim/intermediate_size/vocab_size must be > 0";
+  const char* sizes = "max_tokens/max_seqs/max_labelled/max_position must be > 0";
+  const char* l3msg = "llama3 rope scaling needs 0 < rope_low_freq_factor < rope_high_freq_factor and rope_original_max_position > 0";
+  const char* zmsg = "zero_rank must be in [0, zero_ranks), zero_ranks <= 64";
+  refused(WITH(lora, c.precision = 2), "precision must be TST_PRECISION_BF16 or TST_PRECISION_STRICT");
+  refused(WITH(lora, c.arch = 4), "unsupported arch");
+  refused(WITH(lora, c.arch = -1), "unsupported arch");
+  // the zero-size cases: num_kv_heads = 0 was an integer division by zero, num_layers = 0 a read of layers[0]
+  refused(WITH(lora, c.num_kv_heads = 0), positive);
+  refused(WITH(full, c.num_layers = 0), positive);
+  refused(WITH(lora, c.num_layers = 0), positive);
+  refused(WITH(lora, c.hidden_size = 0), positive);
+  refused(WITH(lora, c.num_heads = 0), positive);
+  refused(WITH(lora, c.head_dim = 0), positive);
+  refused(WITH(lora, c.intermediate_size = 0), positive);
+  refused(WITH(lora, c.vocab_size = 0), positive);
+  refused(WITH(full, c.num_kv_heads = -1), positive);
+  refused(WITH(gpt2, c.vocab_size = -64), positive);
+  refused(WITH(gpt2, c.num_kv_heads = 1), "GPT-2: num_kv_heads must equal num_heads");
+  refused(WITH(gpt2, c.hidden_size = 192), "GPT-2: num_heads * head_dim must equal hidden_size");
+  refused(WITH(lora, c.train_mode = 2), "train_mode must be TST_TRAIN_LORA or TST_TRAIN_FULL");
+  refused(full, "full fine-tune contexts cannot be forked (every fold owns its weights)", true);
+  refused(WITH(lora, c.head_dim = 64), "head_dim must be 128 (GPT-2 family: 64 or 128)");
+  refused(WITH(gpt2, c.head_dim = 32), "GPT-2: num_heads * head_dim must equal hidden_size");
+  refused(WITH(lora, c.hidden_size = 200), "hidden/intermediate/head sizes must be multiples of 64");
+  refused(WITH(lora, c.intermediate_size = 257), "hidden/intermediate/head sizes must be multiples of 64");
+  refused(WITH(lora, c.num_kv_heads = 3), "num_heads must be a multiple of num_kv_heads");
+  refused(WITH(lora, c.max_tokens = 0), sizes);
+  refused(WITH(lora, c.max_seqs = 0), sizes);
+  refused(WITH(lora, c.max_labelled = -1), sizes);
+  refused(WITH(lora, c.max_position = 0), sizes);
+  refused(WITH(lora, c.lora_r = 0), "lora_r must divide 64");
+  refused(WITH(lora, c.lora_r = 24), "lora_r must divide 64");
+  refused(WITH(lora, c.lora_r = 128), "lora_r must divide 64");
+  refused(WITH(lora, c.rope_scaling = 3), "rope_scaling must be TST_ROPE_DEFAULT, TST_ROPE_LINEAR or TST_ROPE_LLAMA3");
+  refused(WITH(linear, c.rope_factor = 0.0f), "rope_factor must be > 0");
+  refused(WITH(l3, c.rope_low_freq_factor = 0.0f), l3msg);
+  refused(WITH(l3, c.rope_high_freq_factor = 1.0f), l3msg);
+  refused(WITH(l3, c.rope_original_max_position = 0), l3msg);
+  refused(WITH(lora, c.n_stack = 9), "n_stack must be <= 8");
+  refused(WITH(full, c.n_stack = 2), "stacked folds need frozen base weights (LoRA): a full fine-tune owns its weights");
+  refused(WITH(r4, c.n_stack = 2), "stacked folds: lora_r must be a multiple of 8");
+  refused(WITH(strict, c.n_stack = 2), "stacked folds are a bf16-path feature: precision = strict runs one fold per context");
+  refused(WITH(lora, c.zero_ranks = 1), "optimizer-state sharding (zero_ranks >= 1) is for full fine-tunes: LoRA state is 0.2 % of the model");
+  refused(WITH(full, c.zero_ranks = 65), zmsg);
+  refused(WITH(WITH(full, c.zero_ranks = 2), c.zero_rank = 2), zmsg);
+  refused(WITH(WITH(full, c.zero_ranks = 2), c.zero_rank = -1), zmsg);
+  refused(WITH(lora, c.lora_targets = 0), "no trainable parameters (lora_targets empty)");
+  refused(WITH(lora, c.lora_targets = 128u), "no trainable parameters (lora_targets empty)");
+  refused(WITH(gpt2, c.lora_targets = 0), "no trainable parameters (lora_targets empty)");
+  // several faults: the first in the engine's order is the one reported
+  refused(WITH(WITH(lora, c.precision = 9), c.arch = 9), "precision must be TST_PRECISION_BF16 or TST_PRECISION_STRICT");
+  refused(WITH(WITH(lora, c.head_dim = 0), c.train_mode = 9), positive);
+  refused(WITH(WITH(lora, c.lora_targets = 0), c.n_stack = 9), "n_stack must be <= 8");
+  // a GPT-2 context has no RoPE: its scaling fields are not looked at; a full fine-tune has no rank or targets
+  CHECK(check_cfg(WITH(gpt2, c.rope_scaling = 3), false, err) == TST_OK);
+  CHECK(check_cfg(WITH(WITH(full, c.lora_r = 0), c.lora_targets = 0), false, err) == TST_OK);
+#undef WITH
+}
+
+// lora_layout: slot 0's table is contiguous, in (layer, group, module) order, n1 = the sum of r (din + rows) over the enabled modules; every single target
+// bit, the full mask, and GPT-2's mapping of the seven bits onto its four Conv1D modules
+static void test_lora_layout() {
+  struct Mod { const char* name; unsigned bits; int din, rows; };
+  for (int arch : {TST_ARCH_LLAMA, TST_ARCH_QWEN3, TST_ARCH_GPT2}) {
+    tst_model_cfg c = valid_cfg(arch, TST_TRAIN_LORA);
+    if (arch == TST_ARCH_QWEN3) { c.num_heads = 4; c.num_kv_heads = 2; c.num_layers = 3; c.intermediate_size = 384; }   // num_heads * head_dim != hidden_size
+    const int d = c.hidden_size, F = c.intermediate_size, dq = c.num_heads * c.head_dim, dkv = c.num_kv_heads * c.head_dim;
+    const std::vector<Mod> mods = arch == TST_ARCH_GPT2
+        ? std::vector<Mod>{{"attn.c_attn", TST_LORA_Q | TST_LORA_K | TST_LORA_V, d, 3 * d}, {"attn.c_proj", TST_LORA_O, d, d}, {"mlp.c_fc", TST_LORA_GATE | TST_LORA_UP, d, F}, {"mlp.c_proj", TST_LORA_DOWN, F, d}}
+        : std::vector<Mod>{{"q_proj", TST_LORA_Q, d, dq}, {"k_proj", TST_LORA_K, d, dkv}, {"v_proj", TST_LORA_V, d, dkv}, {"o_proj", TST_LORA_O, dq, d},
+                           {"gate_proj", TST_LORA_GATE, d, F}, {"up_proj", TST_LORA_UP, d, F}, {"down_proj", TST_LORA_DOWN, F, d}};
+    std::vector<unsigned> masks = {TST_LORA_ALL, TST_LORA_Q | TST_LORA_V, TST_LORA_K | TST_LORA_UP | TST_LORA_DOWN, 0u};
+    for (unsigned b = 1; b <= TST_LORA_DOWN; b <<= 1) masks.push_back(b);
+    for (unsigned mask : masks)
+      for (int r : {8, 16})
+        for (int ns : {1, 3}) {
+          const LoraLayout lay = lora_layout(model_dims(c), r, mask, ns);
+          int64_t at = 0;
+          size_t e = 0;
+          for (int l = 0; l < c.num_layers; ++l)
+            for (const Mod& m : mods) {
+              if (!(mask & m.bits)) continue;
+              CHECK(e + 2 <= lay.entries.size());
+              if (e + 2 > lay.entries.size()) return;
+              const TrainableEntry &A = lay.entries[e], &B = lay.entries[e + 1];
+              const std::string pre = "layers." + std::to_string(l) + "." + m.name;
+              CHECK(A.name == pre + ".lora_A" && A.offset == at && A.rows == r && A.cols == m.din);
+              at += (int64_t)r * m.din;
+              CHECK(B.name == pre + ".lora_B" && B.offset == at && B.rows == m.rows && B.cols == r);
+              at += (int64_t)m.rows * r;
+              e += 2;
+            }
+          CHECK(e == lay.entries.size() && lay.n1 == at && lay.n_train == at * ns && (int)lay.group.size() == 4 * c.num_layers);
+          // the groups: their segments tile the enabled modules' rows in order, and point at the same offsets as the entries
+          int dout[4], din[4];
+          proj_dims(model_dims(c), dout, din);
+          size_t seen = 0;
+          for (size_t g = 0; g < lay.group.size(); ++g) {
+            const LoraGroupLayout& G = lay.group[g];
+            CHECK(G.nseg >= 0 && G.nseg <= 3);
+            for (int q = 0; q < G.nseg; ++q, seen += 2) {
+              CHECK(G.row0[q] >= 0 && G.row0[q] < G.row1[q] && G.row1[q] <= dout[g % 4] && (q == 0 || G.row0[q] >= G.row1[q - 1]));
+              CHECK(G.a_off[q] == lay.entries[seen].offset && G.b_off[q] == lay.entries[seen + 1].offset);
+              CHECK(lay.entries[seen].cols == din[g % 4] && lay.entries[seen + 1].rows == G.row1[q] - G.row0[q]);
+            }
+          }
+          CHECK(seen == lay.entries.size());
+        }
+  }
+}
+
 int main() {
   test_plan_generate();
   test_attribute();
   test_ig();
   test_plan_batch();
   test_zero_and_layout();
+  test_check_cfg();
+  test_lora_layout();
   if (g_fail) { fprintf(stderr, "%d checks failed\n", g_fail); return 1; }
   printf("host_selftest: ok\n");
   return 0;

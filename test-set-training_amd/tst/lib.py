@@ -232,6 +232,8 @@ HOST_SIGNATURES = {
     "tst_host_zero_shard": (C.c_int, [_L, _I, _I, _P]),
     "tst_host_decay_split": (C.c_int, [_L, _L, _L, _P]),
     "tst_host_full_layout": (C.c_int, [_P, _P, _P, _I, _P]),
+    "tst_host_check_cfg": (C.c_int, [_P, _I, _P, _I]),
+    "tst_host_lora_layout": (C.c_int, [_P, _P, _P, _I, _P, _I]),
     "tst_host_stage_ints": (_L, [_P]),
     "tst_host_plan_batch": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I]),
     "tst_host_plan_generate": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I]),
@@ -319,6 +321,23 @@ def host_full_layout(mc):
     d = dict(zip(("n_train", "n_decay", "per_layer", "embed", "wpe", "lm_head", "layer0", "tail"), (int(x) for x in out)))
     d["regions"] = [(int(reg[2 * i]), int(reg[2 * i + 1])) for i in range(nreg.value)]
     return d
+
+
+def host_check_cfg(mc, is_fork=False):
+    """tsthost::check_cfg through the CPU library: (rc, message) -- what tst_create (or, is_fork, tst_fork) answers to ModelCfg `mc` before it allocates anything"""
+    err = C.create_string_buffer(256)
+    rc = load_host().tst_host_check_cfg(C.byref(mc), int(is_fork), err, 256)
+    return int(rc), err.value.decode()
+
+
+def host_lora_layout(mc):
+    """tsthost::lora_layout through the CPU library: dict(n1, n_train, entries=[(name, offset, rows, cols)]) -- one slot's trainable table of a LoRA context"""
+    cap = 14 * max(0, mc.num_layers)   # two entries for each of at most seven modules per layer
+    out, names, ent = (C.c_int64 * 3)(), C.create_string_buffer(128 * max(1, cap)), (C.c_int64 * (3 * max(1, cap)))()
+    if load_host().tst_host_lora_layout(C.byref(mc), out, names, 128, ent, cap) != 0:
+        raise TstError("tst_host_lora_layout: bad arguments")
+    return dict(n1=int(out[0]), n_train=int(out[1]),
+                entries=[(names.raw[128 * i:128 * (i + 1)].split(b"\0", 1)[0].decode(), int(ent[3 * i]), int(ent[3 * i + 1]), int(ent[3 * i + 2])) for i in range(out[2])])
 
 
 def host_plan_batch(mc, ids, labels, cu, seq_slot=None, need_labels=True, trim_last=True, rows=None):
