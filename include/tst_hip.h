@@ -361,6 +361,32 @@ int tst_generate_fetch(tst_ctx* ctx, int32_t* tokens_out /* [n_seqs, max_new_tok
 int tst_generate(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, const int32_t* eos_ids, int32_t n_eos, int32_t* tokens_out, float* logp_out,
                  int32_t* n_new_out);
 
+/* ---- sampled generation: n draws per prompt at one prefill ----
+ * n_samples continuations of every packed prompt of b, each drawn token by token from softmax(logits / temperature) -- the model's own distribution at that
+ * temperature, nothing truncated (no top-k / top-p). Available wherever tst_generate_async is; seq_slot as there. tst_sample_async enqueues ONE prefill over the
+ * n_seqs prompts, the first draw of every (sequence s, sample i) from the prompt's last-row logits, and max_new_tokens - 1 decode steps over the
+ * n_seqs * n_samples decode rows r = s * n_samples + i: a row attends to its prompt's cache rows, which the n samples share, and then to its own tokens. The
+ * draw is Gumbel-max on the device: token = first index of max_v (logit_v / temperature + g_v), g = -log(-log u), u = ((x >> 9) + 0.5) * 2^-23 from the
+ * Philox4x32-10 word x = word (v & 3) of counter (v >> 2, step, i, 0) under the key (low, high 32 bits of seq_seeds[s]). A sequence's draws are thus a function
+ * of its logits, its seed, the step and the sample index only: not of the batch it is in, its place there, or the slot layout. Bit-reproducible.
+ * tst_sample_fetch: tokens_out / logp_out [n_seqs, n_samples, max_new_tokens], n_new_out [n_seqs, n_samples], every (s, i) row cut behind its first eos token as
+ * in tst_generate_fetch; logp_out = log softmax(logits / temperature)[token]. Rows are not compacted when they end: a row does not depend on its neighbours.
+ * The call uses the generation's cache, buffers and pending slot (prompts at cache rows 0 .. n_tokens, the tail of row r at n_tokens + r * max_new_tokens; the
+ * same allocation rule for max_new_tokens): ONE generation of either kind may be pending per context, and a fetch of the other kind returns TST_ESTATE, as does
+ * a fetch without a pending call.
+ * Beside them the first tst_sample_async of a context allocates 8 bytes per max_seqs for the seeds (device, counted in tst_device_bytes, and pinned); a
+ * context that only generates greedily allocates what it did before.
+ * TST_EINVAL before anything is allocated or launched: everything tst_generate_async refuses; n_samples outside 1 .. 64; n_seqs * n_samples > min(max_seqs,
+ * max_labelled) (every draw is a decode row and a head row); n_seqs * n_samples > max_tokens (a decode step is a forward pass over that many token rows --
+ * possible where max_seqs exceeds max_tokens and the prompts are shorter than n_samples tokens); temperature not finite or outside [0.01, 100]; seq_seeds NULL.
+ * Like a greedy generation it reads weights and adapters only. */
+int tst_sample_async(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, int32_t n_samples, float temperature, const uint64_t* seq_seeds /* [n_seqs] */,
+                     const int32_t* eos_ids, int32_t n_eos);
+int tst_sample_fetch(tst_ctx* ctx, int32_t* tokens_out /* [n_seqs, n_samples, max_new_tokens] */, float* logp_out /* same */,
+                     int32_t* n_new_out /* [n_seqs, n_samples] */);
+int tst_sample(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, int32_t n_samples, float temperature, const uint64_t* seq_seeds, const int32_t* eos_ids,
+               int32_t n_eos, int32_t* tokens_out, float* logp_out, int32_t* n_new_out);
+
 /* ---- token attribution: input-gradient saliency of s(x) ----
  * Which tokens of a sequence carry its score. Position p predicts labels[p + 1]; rows(i) = the labelled rows of sequence i, n_i their number, z_r the fp32
  * logits of row r. Per sequence (seq_kind[i]; NULL = all 0):

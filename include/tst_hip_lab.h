@@ -134,6 +134,16 @@ int tst_k_attn_bwd_rope(const void* qkv, int64_t ld, const void* out, int64_t ld
 int tst_k_kv_append(const void* qkv, int64_t ld, int k_off, const int32_t* rows, void* kcache, void* vcache, int T, int Hkv, int dh, int64_t cap_rows);
 int tst_k_attn_decode(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* meta, int n_seqs, int step, void* out, int64_t ldo, int H,
                       int Hkv, int dh, float scale, int64_t cap_rows);
+/* sampled generation kernels (csrc/decode.hip). geo = device int32 {rows R, max_new, n_samples, {pre_row0, len, tail_row0} per decode row r = s n_samples + i};
+ * seeds = device int32 {low, high 32 bits of the seed} per sequence.
+ * attn_decode_shared: attn_decode with key k of row r at cache row k < len ? pre_row0 + k : tail_row0 + k - len (len + step keys).
+ * sample_rows: step j over the fp32 logits row (j == 0 ? s : r) [V of ld]: tok[r, j], logp[r, j] ([R, max_new]), d_ids[r], d_pos[r] = len + j, lab_idx[r] = r. */
+int tst_k_attn_decode_shared(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* geo, int n_rows, int step, void* out, int64_t ldo,
+                             int H, int Hkv, int dh, float scale, int64_t cap_rows);
+int tst_k_attn_decode_shared_f32(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* geo, int n_rows, int step, void* out,
+                                 int64_t ldo, int H, int Hkv, int dh, float scale, int64_t cap_rows);
+int tst_k_sample_rows(const float* logits, int64_t ld, int V, const int32_t* geo, const int32_t* seeds, int n_rows, int j, float inv_temp, int32_t* tok, float* logp,
+                      int32_t* d_ids, int32_t* d_pos, int32_t* lab_idx);
 int tst_k_adamw(float* p, const float* g, float* m, float* v, int64_t n, float max_norm, float lr, float beta1, float beta2, float eps, float wd,
                 int step, float* norm_coef_out /* device [2] */, float* partial_ws /* device [256] */);
 /* the optimizer kernels of csrc/optim.hip one by one; every pointer is a device pointer unless stated, every hook synchronises.

@@ -52,6 +52,14 @@ int tst_host_plan_batch(const tst_model_cfg* cfg, const tst_batch* b, int need_l
  * receive the message of a refusal. Returns TST_OK or TST_EINVAL. */
 int tst_host_plan_generate(const tst_model_cfg* cfg, const tst_batch* b, int max_new, const int32_t* eos_ids, int n_eos, int64_t* out_ints, int32_t* meta_out,
                            int32_t* last_rows_out, int32_t* prefill_rows_out, int32_t* decode_rows_out, char* err_out, int err_cap);
+/* tsthost::plan_sample (sampled generation, include/tst_hip.h tst_sample_async): plan_generate's checks, n_samples in 1 .. 64, n_seqs n_samples <=
+ * min(max_seqs, max_labelled) and <= max_tokens (a decode step's token rows), temperature in [0.01, 100], seq_seeds non-NULL; and the shared-prefix row map: prompts at cache rows 0 .. T, the tail of decode
+ * row r = s n_samples + i at T + r max_new. out_ints[7 + 8] = {S, T, R = S n_samples, cache rows used, cache rows the context allocates for max_new, ints of the
+ * device image, ints allocated for it, slot_r_end[8]}; geo_out [3 + 3 R] (R | max_new | n_samples | {pre_row0, len, tail_row0} per row), seeds_out [2 S] (low,
+ * high word per sequence), last_rows_out [S], prefill_rows_out [T], decode_rows_out [(max_new - 1) R] may each be NULL. Returns TST_OK or TST_EINVAL. */
+int tst_host_plan_sample(const tst_model_cfg* cfg, const tst_batch* b, int max_new, int n_samples, float temperature, const uint64_t* seq_seeds,
+                         const int32_t* eos_ids, int n_eos, int64_t* out_ints, int32_t* geo_out, int32_t* seeds_out, int32_t* last_rows_out, int32_t* prefill_rows_out,
+                         int32_t* decode_rows_out, char* err_out, int err_cap);
 /* the fetch side of a generation: rows of tokens / logp [n_seqs, max_new] are cut behind their first token that is in eos_ids (tokens -1, logp 0 behind it;
  * n_new_out[s] counts the eos token), in place */
 int tst_host_cut_at_eos(int32_t* tokens, float* logp, int32_t* n_new_out, int n_seqs, int max_new, const int32_t* eos_ids, int n_eos);

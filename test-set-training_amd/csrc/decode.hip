@@ -1,4 +1,4 @@
-// Greedy generation (tst_generate_async): the three kernels a decode step adds to the model graph of forward().
+// Generation (tst_generate_async, tst_sample_async): the kernels a decode step adds to the model graph of forward(). Greedy generation has three:
 //
 //   kv_append    copies the k and v columns of qkv [T, ld] -- behind the head norm and RoPE, i.e. as attention reads them -- into one layer's cache
 //                kcache / vcache [rows, Hkv dh] at given row indices. One 16-byte vector per lane, nothing else.
@@ -11,6 +11,11 @@
 //                No atomics. Cache rows >= n of a sequence are never read.
 //   next_token   turns the {lse, logit[target], argmax, max} rows logit_rows leaves in `stats` into the step's outputs and the next step's inputs, on the
 //                device: tok[s, j] = argmax, logp[s, j] = max - lse, d_ids[s] = argmax, d_pos[s] = len[s] + j, lab_idx[s] = s.
+//
+// Sampled generation (tst_sample_async) adds two:
+//   attn_decode, SHARED  the same kernel reading a prompt's cache rows, which the n samples of that prompt share, and behind them the decode row's own tail
+//   sample_rows          logit_rows + next_token of a sampled step in ONE pass over the logits row: the log-sum-exp of logit / temperature and a Gumbel-max
+//                        draw from softmax(logits / temperature), noise from Philox4x32-10
 //
 // The generation's geometry travels in one small device array `meta` (host_logic.h plan_generate writes it):
 //   meta[0] = n_seqs S, meta[1] = max_new, meta[2 .. 2 + S] = cu_seqlens of the prompts, meta[3 + S .. 3 + 2 S) = their lengths.
@@ -69,7 +74,11 @@ __global__ __launch_bounds__(256) void kv_append_kernel(const AT* __restrict__ q
   }
 }
 
-template <typename AT, int DH, int GP>
+// SHARED = false: the greedy generation's contiguous rows (meta as above). SHARED = true: the sampled generation (tst_sample_async) -- `meta` is the geometry
+// array of plan_sample, rows | max_new | n_samples | {pre_row0, len, tail_row0} per decode row; key k of decode row r lies at cache row
+// k < len ? pre_row0 + k : tail_row0 + k - len: the prompt's rows, which the n samples of that prompt share, then the row's own tail. Lane shape, loads per trip
+// and merge order are the one code below, so the same keys give the same bits in either layout.
+template <typename AT, int DH, int GP, bool SHARED>
 __global__ __launch_bounds__(256) void attn_decode_kernel(const AT* __restrict__ q, long ldq, const AT* __restrict__ kcache, const AT* __restrict__ vcache,
                                                           const int* __restrict__ meta, int step, AT* __restrict__ out, long ldo, int G, int Hkv, float scale,
                                                           long cap_rows) {
@@ -78,10 +87,21 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AT* __restrict__
   typedef typename MergeT<AT>::type MT;
   __shared__ MT red[4][GP][LPR * 8 + 2];
   const int s = blockIdx.x, kvh = blockIdx.y;
-  const int S = meta[0], max_new = meta[1];
-  const int n = meta[3 + S + s] + step;                        // keys of this sequence, the new token's included
-  const long row0 = (long)meta[2 + s] + (long)s * max_new;     // cache row of its key 0
-  if (n <= 0 || row0 < 0 || row0 + n > cap_rows) return;       // (plan_generate keeps every sequence inside the cache: never taken)
+  int n, len = 0;
+  long row0, tail0 = 0;
+  if constexpr (SHARED) {
+    row0 = meta[3 + 3 * s];                                    // cache row of the prompt's key 0
+    len = meta[4 + 3 * s];
+    tail0 = meta[5 + 3 * s];                                   // cache row of this decode row's first own token
+    n = len + step;
+    // (plan_sample keeps the prompt and every tail inside the cache: never taken)
+    if (len <= 0 || step < 0 || row0 < 0 || row0 + len > cap_rows || tail0 < 0 || tail0 + step > cap_rows) return;
+  } else {
+    const int S = meta[0], max_new = meta[1];
+    n = meta[3 + S + s] + step;                                // keys of this sequence, the new token's included
+    row0 = (long)meta[2 + s] + (long)s * max_new;              // cache row of its key 0
+    if (n <= 0 || row0 < 0 || row0 + n > cap_rows) return;     // (plan_generate keeps every sequence inside the cache: never taken)
+  }
   const int tid = threadIdx.x, sub = tid % LPR, grp = tid / LPR;
   const int wkv = Hkv * DH;
   float qf[GP][8], acc[GP][8], m[GP], l[GP];
@@ -95,6 +115,11 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AT* __restrict__
   }
   const AT* kp = kcache + row0 * wkv + (long)kvh * DH + sub * 8;
   const AT* vp = vcache + row0 * wkv + (long)kvh * DH + sub * 8;
+  // element offset of key k from kp / vp
+  auto key_off = [&](int k) -> long {
+    if constexpr (SHARED) return (k < len ? (long)k : tail0 - row0 + (k - len)) * wkv;
+    else return (long)k * wkv;
+  };
   auto one_key = [&](const float* kf, const float* vf) {
 #pragma unroll
     for (int g = 0; g < GP; ++g) {
@@ -117,11 +142,11 @@ __global__ __launch_bounds__(256) void attn_decode_kernel(const AT* __restrict__
   for (int j = grp; j < n; j += 2 * NG) {
     float k0[8], v0[8], k1[8], v1[8];
     const bool two = j + NG < n;
-    ld8(kp + (long)j * wkv, k0);
-    ld8(vp + (long)j * wkv, v0);
+    ld8(kp + key_off(j), k0);
+    ld8(vp + key_off(j), v0);
     if (two) {
-      ld8(kp + (long)(j + NG) * wkv, k1);
-      ld8(vp + (long)(j + NG) * wkv, v1);
+      ld8(kp + key_off(j + NG), k1);
+      ld8(vp + key_off(j + NG), v1);
     }
     one_key(k0, v0);
     if (two) one_key(k1, v1);
@@ -198,6 +223,90 @@ __global__ __launch_bounds__(256) void next_token_kernel(const float* __restrict
   lab_idx[s] = s;                   // the head reads every row of a decode step
 }
 
+// ---- sampled generation: Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11), written out; the four output words of
+// counter (c0, c1, c2, c3) under key (k0, k1)
+struct U4 { unsigned x, y, z, w; };
+__device__ __forceinline__ U4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0; c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  return {c0, c1, c2, c3};
+}
+// Gumbel noise of one 32-bit word: u = ((x >> 9) + 0.5) 2^-23 has 24 significant bits (exact in fp32, never 0 or 1), g = -log(-log u)
+__device__ __forceinline__ float gumbel_of(unsigned x) {
+  const float u = ((float)(x >> 9) + 0.5f) * 1.1920928955078125e-07f;
+  return -logf(-logf(u));
+}
+
+// One workgroup per output row r = s n_samples + i: ONE pass over the fp32 logits row src (step 0: the prefill's row s, read by its n samples; afterwards row r)
+// carries the online max / sum of z = logit inv_temp (the log-sum-exp of the tempered row) and the arg-max of fmaf(logit, inv_temp, g) -- Gumbel-max, an exact
+// draw from softmax(logits / temperature). Noise word v & 3 of Philox counter (v >> 2, step, i, 0) under the sequence's seed belongs to vocabulary entry v:
+// one call serves the four columns of a load. Columns >= V (the padding up to ld) are loaded with their vector and never become candidates. Ties go to the
+// first index, as in logit_rows; the partial results are merged in a fixed order: no atomics, bit-reproducible.
+__global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restrict__ logits, long ld, int V, const int* __restrict__ geo,
+                                                          const int* __restrict__ seeds, int j, float inv_temp, int* __restrict__ tok, float* __restrict__ logp,
+                                                          int* __restrict__ d_ids, int* __restrict__ d_pos, int* __restrict__ lab_idx) {
+  __shared__ float red_b[4], red_m[4], red_l[4];
+  __shared__ int red_i[4];
+  const int R = geo[0], max_new = geo[1], n_samples = geo[2];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  if (r >= R || j < 0 || j >= max_new || n_samples < 1) return;
+  const int s = r / n_samples, i = r - s * n_samples;
+  const float* lr = logits + (long)(j == 0 ? s : r) * ld;
+  const unsigned k0 = (unsigned)seeds[2 * s], k1 = (unsigned)seeds[2 * s + 1];
+  float best = -INFINITY, m = -INFINITY, l = 0.f;
+  int bi = 0;
+  for (int c = tid * 4; c < V; c += 1024) {
+    const f32x4 v = *(const f32x4*)(lr + c);
+    const U4 x = philox4x32_10((unsigned)(c >> 2), (unsigned)j, (unsigned)i, 0u, k0, k1);
+    const unsigned xs[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (c + e < V) {
+        const float sc = __builtin_fmaf(v[e], inv_temp, gumbel_of(xs[e]));
+        if (sc > best) { best = sc; bi = c + e; }   // (ascending columns: the first index of a thread's maximum)
+        const float z = v[e] * inv_temp;
+        const float ex = expf(-fabsf(z - m));       // one exponential per entry: the old sum's correction, or the entry's own term (first entry: exp(-inf) = 0)
+        if (z > m) { l = l * ex + 1.0f; m = z; }
+        else l += ex;
+      }
+    }
+  }
+  auto merge = [](float& ma, float& la, float mb, float lb) {
+    const float M = fmaxf(ma, mb);
+    const float wa = ma == -INFINITY ? 0.f : expf(ma - M), wb = mb == -INFINITY ? 0.f : expf(mb - M);
+    la = la * wa + lb * wb;   // (both partners of an exchange form the same two products and one sum)
+    ma = M;
+  };
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ob = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    const float om = __shfl_xor(m, o, 64), ol = __shfl_xor(l, o, 64);
+    merge(m, l, om, ol);
+  }
+  if ((tid & 63) == 0) { red_b[tid >> 6] = best; red_i[tid >> 6] = bi; red_m[tid >> 6] = m; red_l[tid >> 6] = l; }
+  __syncthreads();
+  if (tid == 0) {
+    float bb = red_b[0], M = red_m[0], L = red_l[0];
+    int ba = red_i[0];
+    for (int w = 1; w < 4; ++w) {
+      if (red_b[w] > bb || (red_b[w] == bb && red_i[w] < ba)) { bb = red_b[w]; ba = red_i[w]; }
+      merge(M, L, red_m[w], red_l[w]);
+    }
+    tok[(long)r * max_new + j] = ba;
+    logp[(long)r * max_new + j] = lr[ba] * inv_temp - (M + logf(L));
+    d_ids[r] = ba;
+    d_pos[r] = geo[4 + 3 * r] + j;   // position of the token just chosen: the prompt's length + j
+    lab_idx[r] = r;                  // the head reads every row of a decode step
+  }
+}
+
 }  // namespace
 
 template <typename AT>
@@ -223,7 +332,28 @@ int attn_decode(hipStream_t st, const AT* q, long ldq, const AT* kcache, const A
   const int G = H / Hkv;
   const dim3 grid((unsigned)n_seqs, (unsigned)Hkv);
 #define AD_LAUNCH(DH, GP) \
-  hipLaunchKernelGGL((attn_decode_kernel<AT, DH, GP>), grid, dim3(256), 0, st, q, ldq, kcache, vcache, meta, step, out, ldo, G, Hkv, scale, cap_rows)
+  hipLaunchKernelGGL((attn_decode_kernel<AT, DH, GP, false>), grid, dim3(256), 0, st, q, ldq, kcache, vcache, meta, step, out, ldo, G, Hkv, scale, cap_rows)
+#define AD_DH(GP) do { if (dh == 128) AD_LAUNCH(128, GP); else AD_LAUNCH(64, GP); } while (0)
+  if (G == 1) AD_DH(1);
+  else if (G == 2) AD_DH(2);
+  else if (G <= 4) AD_DH(4);
+  else AD_DH(8);
+#undef AD_DH
+#undef AD_LAUNCH
+  return CHECK_LAUNCH();
+}
+
+template <typename AT>
+int attn_decode_shared(hipStream_t st, const AT* q, long ldq, const AT* kcache, const AT* vcache, const int* geo, int n_rows, int step, AT* out, long ldo, int H,
+                       int Hkv, int dh, float scale, long cap_rows) {
+  if (n_rows <= 0) return TST_OK;
+  if (!q || !kcache || !vcache || !geo || !out || Hkv < 1 || H < Hkv || H % Hkv || H / Hkv > 8 || (dh != 64 && dh != 128) || (ldq & 7) || (ldo & 7) ||
+      ldq < (long)H * dh || ldo < (long)H * dh || step < 0 || cap_rows <= 0 || Hkv > 65535)
+    return TST_EINVAL;
+  const int G = H / Hkv;
+  const dim3 grid((unsigned)n_rows, (unsigned)Hkv);
+#define AD_LAUNCH(DH, GP) \
+  hipLaunchKernelGGL((attn_decode_kernel<AT, DH, GP, true>), grid, dim3(256), 0, st, q, ldq, kcache, vcache, geo, step, out, ldo, G, Hkv, scale, cap_rows)
 #define AD_DH(GP) do { if (dh == 128) AD_LAUNCH(128, GP); else AD_LAUNCH(64, GP); } while (0)
   if (G == 1) AD_DH(1);
   else if (G == 2) AD_DH(2);
@@ -241,9 +371,20 @@ int next_token(hipStream_t st, const float* stats, const int* meta, int n_seqs, 
   return CHECK_LAUNCH();
 }
 
+int sample_rows(hipStream_t st, const float* logits, long ld, int V, const int* geo, const int* seeds, int n_rows, int j, float inv_temp, int* tok, float* logp,
+                int* d_ids, int* d_pos, int* lab_idx) {
+  if (n_rows <= 0) return TST_OK;
+  if (!logits || !geo || !seeds || !tok || !logp || !d_ids || !d_pos || !lab_idx || j < 0 || V < 1 || (ld & 3) || ld < (((long)V + 3) & ~3L) || !(inv_temp > 0.f))
+    return TST_EINVAL;
+  hipLaunchKernelGGL(sample_rows_kernel, dim3((unsigned)n_rows), dim3(256), 0, st, logits, ld, V, geo, seeds, j, inv_temp, tok, logp, d_ids, d_pos, lab_idx);
+  return CHECK_LAUNCH();
+}
+
 #define INSTANTIATE(AT)                                                                                                           \
   template int kv_append<AT>(hipStream_t, const AT*, long, int, const int*, AT*, AT*, int, int, int, long);                      \
   template int attn_decode<AT>(hipStream_t, const AT*, long, const AT*, const AT*, const int*, int, int, AT*, long, int, int, int, \
-                               float, long);
+                               float, long);                                                                                        \
+  template int attn_decode_shared<AT>(hipStream_t, const AT*, long, const AT*, const AT*, const int*, int, int, AT*, long, int, int, \
+                                      int, float, long);
 INSTANTIATE(bf16_t)
 INSTANTIATE(float)

@@ -294,7 +294,9 @@ struct tst_ctx {
   float* gen_logp = nullptr;
   int* h_gen = nullptr;         // pinned: staging image of gen_dev | tokens [Smax, cap_new] | logp [Smax, cap_new] of the pending generation
   hipEvent_t gen_evt = nullptr; // recorded behind the result copies: tst_generate_fetch waits for it, not for the stream
-  int gen_S = -1, gen_new = 0;  // pending generation (-1: none)
+  int gen_S = -1, gen_new = 0;  // pending generation (-1: none); a sampled one (tst_sample_async) shares the slot: gen_S counts its decode rows
+  int gen_samples = 0;          // 0: the pending generation is greedy; n >= 1: sampled with n draws per prompt
+  int *smp_seeds = nullptr, *h_smp_seeds = nullptr;   // sampled generations: low | high word of every sequence's seed [2 Smax] and its pinned staging image (first tst_sample_async)
   std::vector<int> gen_eos;
   // Token attribution (tst_attribute_async; kernels in attribute.hip, row weights and the fetch side in host_logic.h). Allocated by the first attribution of the
   // context. attr_dev = row weights [Rmax] | row kinds [Rmax] | option ids [256] | gxi [Tmax] | gnorm [Tmax] (4-byte words); h_attr = the pinned staging image of the
@@ -1039,9 +1041,11 @@ int tail_fwd(CtxT<AT>* ctx, LayerT<AT>& W, const Rows& rows, const TailBufsT<AT>
 }
 
 // what a generation asks of forward(): mode 0 = the graph every other entry point runs; 1 = the prefill (RoPE as its own pass, k | v of every layer appended to
-// the cache); 2 = decode step `step` (one row per sequence, positions from d_pos, attn_decode against the cache)
+// the cache); 2 = decode step `step` (one row per sequence, positions from d_pos, attn_decode against the cache). shared: a sampled generation -- gen_dev
+// holds plan_sample's image, a decode row attends to its prompt's shared rows and its own tail (attn_decode_shared)
 struct GenPass {
   int mode = 0, step = 0;
+  bool shared = false;
 };
 
 // what an attribution asks of its passes. backward: true = backward() is seeded by attr_seed instead of the loss gradient, forms the gradient of layer 0's input in
@@ -1101,10 +1105,14 @@ int forward(CtxT<AT>* ctx, bool stash, GenPass gen = {}, AttrPass ap = {}) {
       AT* kc = (AT*)ctx->gen_kv + (long)l * 2 * ctx->gen_rows * wkv;
       AT* vc = kc + ctx->gen_rows * wkv;
       const int S = ctx->cur_S;
-      const int* krows = ctx->gen_dev + (3 + 2 * ctx->Smax) + (gen.mode == 1 ? 0L : ctx->Tmax + (long)(gen.step - 1) * S);
+      const long o_pre = gen.shared ? (long)tsthost::sample_off_prefill(batch_limits(ctx)) : 3 + 2 * ctx->Smax;
+      const int* krows = ctx->gen_dev + o_pre + (gen.mode == 1 ? 0L : ctx->Tmax + (long)(gen.step - 1) * S);
       CTX_RC(kv_append<AT>(st, A.qkv, ctx->dqkv, ctx->dq, krows, kc, vc, T, ctx->Hkv, ctx->dh, ctx->gen_rows));
       if (gen.mode == 2) {
         const int slot = prof_begin(ctx, st, ctx->prof_hbm);
+        if (gen.shared)
+          CTX_RC(attn_decode_shared<AT>(st, A.qkv, ctx->dqkv, kc, vc, ctx->gen_dev, S, gen.step, A.attn, ctx->dattn, ctx->H, ctx->Hkv, ctx->dh, scale, ctx->gen_rows));
+        else
         CTX_RC(attn_decode<AT>(st, A.qkv, ctx->dqkv, kc, vc, ctx->gen_dev, S, gen.step, A.attn, ctx->dattn, ctx->H, ctx->Hkv, ctx->dh, scale, ctx->gen_rows));
         prof_end(ctx, st, slot, PROF_ATTN, 1, 4.0 * ctx->cur_sumsq_len * ctx->H * ctx->dh);   // q . K^T + P . V over the cached keys (cur_sumsq_len = their count)
       }
@@ -2578,6 +2586,85 @@ int generate_async_impl(CtxT<AT>* ctx, const tst_batch* b, int32_t max_new, cons
   ctx->gen_eos.assign(eos_ids, eos_ids + n_eos);
   ctx->gen_S = S;
   ctx->gen_new = max_new;
+  ctx->gen_samples = 0;
+  return TST_OK;
+}
+
+// ---- sampled generation: ONE prefill over the S prompts, then n_samples draws of each as S n_samples decode rows that share the prompt's cache rows
+// (include/tst_hip.h tst_sample_async; kernels in decode.hip, row map in host_logic.h plan_sample). The cache, the device image, the output block and the pending
+// slot are the greedy generation's.
+// the seeds of a sampled generation: 8 bytes per max_seqs on the device and pinned, allocated by the first tst_sample_async of a context and counted in
+// tst_device_bytes (the generation's own image has no room for them: geo | prefill rows | decode rows fill it exactly)
+int sample_reserve(tst_ctx* ctx) {
+  if (!ctx->smp_seeds) {
+    ctx->smp_seeds = (int*)ctx->pool.alloc(8 * (int64_t)ctx->Smax);
+    if (!ctx->smp_seeds) return fail(ctx, TST_ENOMEM, "hipMalloc failed: seeds of the sampled generation");
+    CTX_HIP(hipStreamSynchronize(nullptr));   // (the pool's zero fill, as in gen_reserve)
+  }
+  if (!ctx->h_smp_seeds) CTX_HIP(hipHostMalloc((void**)&ctx->h_smp_seeds, 8 * (size_t)ctx->Smax, hipHostMallocDefault));
+  return TST_OK;
+}
+
+template <typename AT>
+int sample_async_impl(CtxT<AT>* ctx, const tst_batch* b, int32_t max_new, int32_t n_samples, float temperature, const uint64_t* seq_seeds, const int32_t* eos_ids,
+                      int32_t n_eos) {
+  if (!b) return TST_EINVAL;
+  if (!ctx->finalized) return fail(ctx, TST_ESTATE, "weights not finalised");
+  ctx->err.clear();
+  const tsthost::BatchLimits lim = batch_limits(ctx);
+  tsthost::SamplePlan plan;
+  {
+    std::string perr;
+    if (tsthost::plan_sample(b, lim, max_new, n_samples, temperature, seq_seeds, eos_ids, n_eos, plan, perr) != TST_OK) return fail(ctx, TST_EINVAL, perr);
+  }
+  if (ctx->H % ctx->Hkv || ctx->H / ctx->Hkv > 8 || (ctx->dh != 64 && ctx->dh != 128))
+    return fail(ctx, TST_EINVAL, "generation needs head_dim 64 or 128 and at most 8 query heads per kv head");
+  hipStream_t st = ctx->stream;
+  const int S = plan.S, R = plan.R;
+  CTX_RC(upload_batch(ctx, b, false, plan.last_rows.data(), S));   // (refuses a host id outside the vocabulary before the cache is allocated or grown)
+  ctx->gen_S = -1;
+  CTX_RC(gen_reserve(ctx, max_new));
+  CTX_RC(sample_reserve(ctx));
+  CTX_RC(ctx_event_sync(ctx, ctx->gen_evt));   // the staging images may still feed the previous generation's copies
+  const size_t o_pre = tsthost::sample_off_prefill(lim), o_dec = tsthost::sample_off_decode(lim);
+  {
+    int* h = ctx->h_gen;
+    memcpy(h, plan.geo.data(), plan.geo.size() * sizeof(int));
+    memcpy(ctx->h_smp_seeds, plan.seeds.data(), plan.seeds.size() * sizeof(int));
+    CTX_HIP(hipMemcpyAsync(ctx->smp_seeds, ctx->h_smp_seeds, plan.seeds.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    memcpy(h + o_pre, plan.prefill_rows.data(), plan.prefill_rows.size() * sizeof(int));
+    if (!plan.decode_rows.empty()) memcpy(h + o_dec, plan.decode_rows.data(), plan.decode_rows.size() * sizeof(int));
+    CTX_HIP(hipMemcpyAsync(ctx->gen_dev, h, (o_dec + plan.decode_rows.size()) * sizeof(int), hipMemcpyHostToDevice, st));
+  }
+  const float inv_temp = 1.0f / temperature;
+  auto step_tail = [&](int j) -> int {
+    CTX_RC(head_forward(ctx, false));   // step 0: the S last rows of the prompts; afterwards the R decode rows
+    return sample_rows(st, ctx->logits, ctx->Vp, ctx->V, ctx->gen_dev, ctx->smp_seeds, R, j, inv_temp, ctx->gen_tok, ctx->gen_logp, ctx->d_ids, ctx->d_pos,
+                       ctx->d_lab_idx);
+  };
+  CTX_RC(forward(ctx, false, GenPass{1, 0, true}));   // prefill
+  CTX_RC(step_tail(0));
+  if (max_new > 1) {
+    // decode steps: forward() over one row per draw; the slot boundaries are decode-row counts (rows are s-major: a stacked context's slot order is kept)
+    ctx->cur_T = ctx->cur_S = ctx->cur_R = R;
+    ctx->cur_maxlen = 1;
+    for (int q = 0; q < TST_MAX_STACK; ++q) ctx->slot_ends.t_end[q] = ctx->row_ends.t_end[q] = plan.slot_r_end[q];
+    double keys = (double)plan.T * n_samples;
+    for (int j = 1; j < max_new; ++j) {
+      keys += R;
+      ctx->cur_sumsq_len = keys;
+      CTX_RC(forward(ctx, false, GenPass{2, j, true}));
+      CTX_RC(step_tail(j));
+    }
+  }
+  float* h_out = (float*)(ctx->h_gen + ctx->gen_dev_bytes / 4);
+  CTX_HIP(hipMemcpyAsync(h_out, ctx->gen_tok, (size_t)R * max_new * 4, hipMemcpyDeviceToHost, st));
+  CTX_HIP(hipMemcpyAsync(h_out + (size_t)ctx->Smax * ctx->gen_cap_new, ctx->gen_logp, (size_t)R * max_new * 4, hipMemcpyDeviceToHost, st));
+  CTX_HIP(hipEventRecord(ctx->gen_evt, st));
+  ctx->gen_eos.assign(eos_ids, eos_ids + n_eos);
+  ctx->gen_S = R;
+  ctx->gen_new = max_new;
+  ctx->gen_samples = n_samples;
   return TST_OK;
 }
 
@@ -2873,6 +2960,7 @@ int tst_destroy(tst_ctx* ctx) {
   if (ctx->h_score) (void)hipHostFree(ctx->h_score);
   if (ctx->h_gen) (void)hipHostFree(ctx->h_gen);
   if (ctx->h_attr) (void)hipHostFree(ctx->h_attr);
+  if (ctx->h_smp_seeds) (void)hipHostFree(ctx->h_smp_seeds);
   if (ctx->h_ig) (void)hipHostFree(ctx->h_ig);
   if (ctx->attr_evt) (void)hipEventDestroy(ctx->attr_evt);
   if (ctx->gen_evt) (void)hipEventDestroy(ctx->gen_evt);
@@ -3304,10 +3392,10 @@ int tst_generate_async(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens,
   return typed(ctx, [&](auto* c) { return generate_async_impl(c, b, max_new_tokens, eos_ids, n_eos); });
 }
 
-int tst_generate_fetch(tst_ctx* ctx, int32_t* tokens_out, float* logp_out, int32_t* n_new_out) {
+// the fetch side of both kinds of generation: S rows of the pinned output block, each cut behind its first eos token
+static int gen_fetch_rows(tst_ctx* ctx, const char* what, int32_t* tokens_out, float* logp_out, int32_t* n_new_out) {
   int S;
-  if (!ctx) return TST_EINVAL;
-  CTX_RC(take_pending(ctx, ctx->gen_S, ctx->gen_evt, "tst_generate_fetch without a pending tst_generate_async", S));
+  CTX_RC(take_pending(ctx, ctx->gen_S, ctx->gen_evt, what, S));
   const int n = ctx->gen_new;
   const int32_t* h_tok = (const int32_t*)(ctx->h_gen + ctx->gen_dev_bytes / 4);
   const float* h_lp = (const float*)h_tok + (size_t)ctx->Smax * ctx->gen_cap_new;
@@ -3319,6 +3407,31 @@ int tst_generate_fetch(tst_ctx* ctx, int32_t* tokens_out, float* logp_out, int32
   if (logp_out) memcpy(logp_out, lp.data(), lp.size() * 4);
   if (n_new_out) memcpy(n_new_out, nn.data(), nn.size() * 4);
   return TST_OK;
+}
+
+int tst_generate_fetch(tst_ctx* ctx, int32_t* tokens_out, float* logp_out, int32_t* n_new_out) {
+  if (!ctx) return TST_EINVAL;
+  if (ctx->gen_S >= 0 && ctx->gen_samples > 0) return fail(ctx, TST_ESTATE, "the pending generation is a tst_sample_async: fetch it with tst_sample_fetch");
+  return gen_fetch_rows(ctx, "tst_generate_fetch without a pending tst_generate_async", tokens_out, logp_out, n_new_out);
+}
+
+int tst_sample_async(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, int32_t n_samples, float temperature, const uint64_t* seq_seeds,
+                     const int32_t* eos_ids, int32_t n_eos) {
+  if (!ctx || !b) return TST_EINVAL;
+  return typed(ctx, [&](auto* c) { return sample_async_impl(c, b, max_new_tokens, n_samples, temperature, seq_seeds, eos_ids, n_eos); });
+}
+
+int tst_sample_fetch(tst_ctx* ctx, int32_t* tokens_out, float* logp_out, int32_t* n_new_out) {
+  if (!ctx) return TST_EINVAL;
+  if (ctx->gen_S >= 0 && ctx->gen_samples == 0) return fail(ctx, TST_ESTATE, "the pending generation is a tst_generate_async: fetch it with tst_generate_fetch");
+  return gen_fetch_rows(ctx, "tst_sample_fetch without a pending tst_sample_async", tokens_out, logp_out, n_new_out);
+}
+
+int tst_sample(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, int32_t n_samples, float temperature, const uint64_t* seq_seeds, const int32_t* eos_ids,
+               int32_t n_eos, int32_t* tokens_out, float* logp_out, int32_t* n_new_out) {
+  int rc = tst_sample_async(ctx, b, max_new_tokens, n_samples, temperature, seq_seeds, eos_ids, n_eos);
+  if (rc != TST_OK) return rc;
+  return tst_sample_fetch(ctx, tokens_out, logp_out, n_new_out);
 }
 
 int tst_generate(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, const int32_t* eos_ids, int32_t n_eos, int32_t* tokens_out, float* logp_out,

@@ -108,6 +108,31 @@ int tst_host_plan_generate(const tst_model_cfg* cfg, const tst_batch* b, int max
   return TST_OK;
 }
 
+int tst_host_plan_sample(const tst_model_cfg* cfg, const tst_batch* b, int max_new, int n_samples, float temperature, const uint64_t* seq_seeds,
+                         const int32_t* eos_ids, int n_eos, int64_t* out_ints, int32_t* geo_out, int32_t* seeds_out, int32_t* last_rows_out, int32_t* prefill_rows_out,
+                         int32_t* decode_rows_out, char* err_out, int err_cap) {
+  if (!cfg || !out_ints) return TST_EINVAL;
+  tsthost::SamplePlan g;
+  std::string err;
+  const tsthost::BatchLimits lim = limits_of(*cfg);
+  const int rc = tsthost::plan_sample(b, lim, max_new, n_samples, temperature, seq_seeds, eos_ids, n_eos, g, err);
+  if (err_out && err_cap > 0) {
+    strncpy(err_out, err.c_str(), (size_t)err_cap - 1);
+    err_out[err_cap - 1] = 0;
+  }
+  if (rc != TST_OK) return rc;
+  int64_t* o = out_ints;
+  *o++ = g.S; *o++ = g.T; *o++ = g.R; *o++ = g.rows_used; *o++ = tsthost::gen_cache_rows(lim, max_new);
+  *o++ = (int64_t)tsthost::sample_dev_ints(lim, max_new); *o++ = (int64_t)tsthost::gen_dev_ints(lim, max_new);
+  for (int q = 0; q < tsthost::kMaxStack; ++q) *o++ = g.slot_r_end[q];
+  auto put = [](int32_t* dst, const std::vector<int>& v) {
+    if (dst)
+      for (size_t i = 0; i < v.size(); ++i) dst[i] = v[i];
+  };
+  put(geo_out, g.geo); put(seeds_out, g.seeds); put(last_rows_out, g.last_rows); put(prefill_rows_out, g.prefill_rows); put(decode_rows_out, g.decode_rows);
+  return TST_OK;
+}
+
 int tst_host_cut_at_eos(int32_t* tokens, float* logp, int32_t* n_new_out, int n_seqs, int max_new, const int32_t* eos_ids, int n_eos) {
   if (!tokens || n_seqs < 0 || max_new < 1 || n_eos < 0 || (n_eos > 0 && !eos_ids)) return TST_EINVAL;
   tsthost::cut_at_eos(tokens, logp, n_new_out, n_seqs, max_new, eos_ids, n_eos);

@@ -372,6 +372,68 @@ inline int plan_generate(const tst_batch* b, const BatchLimits& lim, int max_new
   out.rows_used = (long)T + (long)S * max_new;
   return TST_OK;
 }
+// ------------------------------------------------------------------------------------------------ sampled generation: validation + the shared-prefix row map
+// tst_sample_async draws n_samples continuations of every prompt at one prefill: decode row r = s n_samples + i (s-major, so a stacked context's slot order is
+// kept) attends to its prompt's cache rows, which the n samples share, and then to its own tail. The prompts are packed at cache rows 0 .. T; the tail of decode row
+// r starts at T + r max_new. That fits gen_cache_rows because S n_samples <= max_seqs. A decode step is a forward pass over S n_samples token rows, so that
+// product is held to max_tokens as well. plan_sample refuses what the engine cannot run BEFORE anything is launched
+// and fills the staging image of the generation's device array (offsets: sample_off_*):
+//   geo          [3 + 3 R]        R | max_new | n_samples | {pre_row0, len, tail_row0} per decode row    (what attn_decode_shared / sample_rows read)
+//   seeds        [2 S]            low, high 32 bits of seq_seeds[s]: the Philox key of sequence s (a small device array of its own: geo | prefill_rows |
+//                                 decode_rows fill exactly the ints a greedy generation's image has, gen_dev_ints)
+//   last_rows    [S]              packed index of every prompt's last token: the rows the prefill's head runs on
+//   prefill_rows [T]              cache row of every prompt token (its packed index)
+//   decode_rows  [(max_new-1) R]  cache row of the token decode step j = 1 .. max_new - 1 appends for decode row r (the one step j - 1 drew), at [(j - 1) R + r]
+//   slot_r_end   [kMaxStack]      decode rows of slots 0 .. q: plan_generate's slot_s_end times n_samples
+constexpr int kSampleMaxN = 64;
+constexpr float kSampleMinTemp = 0.01f, kSampleMaxTemp = 100.0f;
+inline size_t sample_off_prefill(const BatchLimits& l) { return (size_t)3 + 3 * (size_t)l.Smax; }
+inline size_t sample_off_decode(const BatchLimits& l) { return sample_off_prefill(l) + (size_t)l.Tmax; }
+// ints of a sampled generation's image at capacity (== gen_dev_ints)
+inline size_t sample_dev_ints(const BatchLimits& l, int max_new) { return sample_off_decode(l) + (size_t)l.Smax * (size_t)(max_new - 1); }
+struct SamplePlan {
+  int S = 0, T = 0, R = 0, max_new = 0, n_samples = 0;
+  long rows_used = 0;   // rows of the cache this generation touches (<= gen_cache_rows)
+  std::vector<int> geo, seeds, last_rows, prefill_rows, decode_rows;
+  int slot_r_end[kMaxStack];
+};
+inline int plan_sample(const tst_batch* b, const BatchLimits& lim, int max_new, int n_samples, float temperature, const uint64_t* seq_seeds, const int32_t* eos_ids,
+                       int n_eos, SamplePlan& out, std::string& err) {
+  auto fail = [&](const char* m) { err = m; return TST_EINVAL; };
+  GenPlan g;
+  if (const int rc = plan_generate(b, lim, max_new, eos_ids, n_eos, g, err)) return rc;
+  if (n_samples < 1 || n_samples > kSampleMaxN) return fail("n_samples out of range (1..64)");
+  const long R = (long)g.S * n_samples;
+  if (R > lim.Smax || R > lim.Rmax) return fail("n_seqs * n_samples exceeds max_seqs or max_labelled: every draw is a decode row");
+  // a decode step runs the model over R token rows: the activation buffers, ids and positions hold max_tokens of them (a greedy step has n_seqs <= n_tokens rows)
+  if (R > lim.Tmax) return fail("n_seqs * n_samples exceeds max_tokens: every draw is a token row of a decode step");
+  if (!(temperature >= kSampleMinTemp && temperature <= kSampleMaxTemp)) return fail("temperature must be finite and in [0.01, 100]");   // (a NaN fails both)
+  if (!seq_seeds) return fail("null seq_seeds");
+  const int S = g.S, T = g.T;
+  out.S = S; out.T = T; out.R = (int)R; out.max_new = max_new; out.n_samples = n_samples;
+  out.geo.assign((size_t)3 + 3 * (size_t)R, 0);
+  out.seeds.assign(2 * (size_t)S, 0);
+  out.last_rows = g.last_rows;
+  out.prefill_rows.assign((size_t)T, 0);
+  out.decode_rows.assign((size_t)(max_new - 1) * (size_t)R, 0);
+  out.geo[0] = (int)R; out.geo[1] = max_new; out.geo[2] = n_samples;
+  for (int t = 0; t < T; ++t) out.prefill_rows[(size_t)t] = t;
+  for (int s = 0; s < S; ++s) {
+    out.seeds[2 * (size_t)s] = (int)(uint32_t)(seq_seeds[s] & 0xffffffffu);
+    out.seeds[2 * (size_t)s + 1] = (int)(uint32_t)(seq_seeds[s] >> 32);
+    for (int i = 0; i < n_samples; ++i) {
+      const size_t r = (size_t)s * n_samples + i;
+      const int tail0 = T + (int)r * max_new;
+      out.geo[3 + 3 * r] = g.meta[(size_t)2 + s];
+      out.geo[4 + 3 * r] = g.meta[(size_t)3 + S + s];
+      out.geo[5 + 3 * r] = tail0;
+      for (int j = 1; j < max_new; ++j) out.decode_rows[(size_t)(j - 1) * R + r] = tail0 + j - 1;
+    }
+  }
+  for (int q = 0; q < kMaxStack; ++q) out.slot_r_end[q] = g.slot_s_end[q] * n_samples;
+  out.rows_used = (long)T + R * max_new;
+  return TST_OK;
+}
 // the fetch side: row s of tokens / logp [S, max_new] is cut behind its first token that is in eos_ids -- n_new[s] counts that token, the entries behind
 // it become -1 / 0; without a hit n_new[s] = max_new. In place.
 inline void cut_at_eos(int32_t* tokens, float* logp, int32_t* n_new, int S, int max_new, const int32_t* eos_ids, int n_eos) {

@@ -273,6 +273,82 @@ static void test_plan_generate() {
   CHECK(n_new[1] == 4);
 }
 
+// plan_sample: prompts at rows 0 .. T, one tail of max_new rows per decode row behind them -- inside the cache, no tail overlapping another or a prompt; the
+// device image inside what gen_reserve allocates; slot boundaries times n_samples; every refusal. Random ragged prompt batches, arrays at their exact sizes.
+static void test_plan_sample() {
+  std::mt19937 rng(47u);
+  for (int it = 0; it < 300; ++it) {
+    const int ns = (it % 3 == 0) ? 1 + (int)(rng() % 4u) : 1;
+    const int S = ns + (int)(rng() % 6u), max_len = 1 + (int)(rng() % 40u), V = 50, max_new = 1 + (int)(rng() % 9u), n = 1 + (int)(rng() % 8u);
+    Batch x = make_batch(rng, S, max_len, V, ns, false);
+    x.b.input_ids = (const int32_t*)(uintptr_t)16;   // never dereferenced
+    const int R = S * n;
+    const BatchLimits lim = {std::max(x.b.n_tokens, R) + (int)(rng() % 3u), R + (int)(rng() % 3u), R, V, max_len + max_new, ns};
+    const int32_t eos[2] = {0, V - 1};
+    std::vector<uint64_t> seeds((size_t)S);
+    for (auto& v : seeds) v = ((uint64_t)rng() << 32) | rng();
+    SamplePlan g;
+    std::string err;
+    CHECK(plan_sample(&x.b, lim, max_new, n, 1.0f, seeds.data(), eos, 2, g, err) == TST_OK);
+    const long cap = gen_cache_rows(lim, max_new);
+    const int T = x.b.n_tokens;
+    CHECK(g.S == S && g.T == T && g.R == R && R <= lim.Tmax && g.rows_used <= cap && g.rows_used == (long)T + (long)R * max_new);
+    CHECK((int)g.geo.size() == 3 + 3 * R && g.geo[0] == R && g.geo[1] == max_new && g.geo[2] == n && (int)g.decode_rows.size() == (max_new - 1) * R);
+    CHECK((int)g.seeds.size() == 2 * S && (int)g.prefill_rows.size() == T && (int)g.last_rows.size() == S);
+    // the image fits what the context allocates, every part at its offset
+    CHECK(sample_dev_ints(lim, max_new) == gen_dev_ints(lim, max_new));
+    CHECK(g.geo.size() <= sample_off_prefill(lim));
+    CHECK(sample_off_prefill(lim) + g.prefill_rows.size() <= sample_off_decode(lim) && sample_off_decode(lim) + g.decode_rows.size() <= sample_dev_ints(lim, max_new));
+    std::vector<char> seen((size_t)cap, 0);
+    for (int t = 0; t < T; ++t) {
+      const int row = g.prefill_rows[(size_t)t];
+      CHECK(row == t);
+      if (row >= 0 && row < cap) { CHECK(!seen[(size_t)row]); seen[(size_t)row] = 1; }
+    }
+    for (int s = 0; s < S; ++s) {
+      const int s0 = x.cu[(size_t)s], len = x.cu[(size_t)s + 1] - s0;
+      CHECK(g.last_rows[(size_t)s] == s0 + len - 1);
+      CHECK((uint32_t)g.seeds[2 * (size_t)s] == (uint32_t)seeds[(size_t)s] && (uint32_t)g.seeds[2 * (size_t)s + 1] == (uint32_t)(seeds[(size_t)s] >> 32));
+      for (int i = 0; i < n; ++i) {
+        const int r = s * n + i;
+        const int pre0 = g.geo[3 + 3 * (size_t)r], tail0 = g.geo[5 + 3 * (size_t)r];
+        CHECK(pre0 == s0 && g.geo[4 + 3 * (size_t)r] == len && tail0 == T + r * max_new && (long)tail0 + max_new <= g.rows_used);
+        for (int j = 0; j < max_new; ++j) {   // the whole tail is the row's own (its last row is reserved, never written: max_new - 1 appends)
+          const int row = tail0 + j;
+          if (j + 1 < max_new) CHECK(g.decode_rows[(size_t)j * R + r] == row);
+          if (row >= 0 && row < cap) { CHECK(!seen[(size_t)row]); seen[(size_t)row] = 1; }
+        }
+      }
+    }
+    for (int q = 0; q < kMaxStack; ++q) {
+      int want = 0;
+      for (int s = 0; s < S; ++s) want += (ns > 1 ? x.slot[(size_t)s] : 0) <= q;
+      CHECK(g.slot_r_end[q] == want * n);
+    }
+    // refusals: plan_generate's own, then what sampling adds
+    SamplePlan r;
+    CHECK(plan_sample(&x.b, lim, 0, n, 1.0f, seeds.data(), eos, 2, r, err) == TST_EINVAL && err.find("max_new_tokens") != std::string::npos);
+    const int32_t bad_eos[1] = {V};
+    CHECK(plan_sample(&x.b, lim, max_new, n, 1.0f, seeds.data(), bad_eos, 1, r, err) == TST_EINVAL && err.find("eos id") != std::string::npos);
+    BatchLimits shortpos = lim; shortpos.max_position = 1;
+    CHECK(plan_sample(&x.b, shortpos, max_new, n, 1.0f, seeds.data(), nullptr, 0, r, err) == TST_EINVAL && err.find("max_position") != std::string::npos);
+    CHECK(plan_sample(nullptr, lim, max_new, n, 1.0f, seeds.data(), nullptr, 0, r, err) == TST_EINVAL);
+    CHECK(plan_sample(&x.b, lim, max_new, 0, 1.0f, seeds.data(), nullptr, 0, r, err) == TST_EINVAL && err.find("n_samples") != std::string::npos);
+    CHECK(plan_sample(&x.b, lim, max_new, kSampleMaxN + 1, 1.0f, seeds.data(), nullptr, 0, r, err) == TST_EINVAL && err.find("n_samples") != std::string::npos);
+    BatchLimits few = lim; few.Rmax = R - 1;
+    if (few.Rmax >= S) CHECK(plan_sample(&x.b, few, max_new, n, 1.0f, seeds.data(), nullptr, 0, r, err) == TST_EINVAL && err.find("n_seqs * n_samples") != std::string::npos);
+    few = lim; few.Smax = R - 1;
+    if (few.Smax >= S) CHECK(plan_sample(&x.b, few, max_new, n, 1.0f, seeds.data(), nullptr, 0, r, err) == TST_EINVAL && err.find("n_seqs * n_samples") != std::string::npos);
+    few = lim; few.Tmax = R - 1;   // rows fit max_seqs and max_labelled, not max_tokens (possible where the prompts are shorter than n_samples tokens)
+    if (few.Tmax >= x.b.n_tokens) CHECK(plan_sample(&x.b, few, max_new, n, 1.0f, seeds.data(), nullptr, 0, r, err) == TST_EINVAL && err.find("exceeds max_tokens") != std::string::npos);
+    for (float bad : {0.0f, 0.009f, 100.5f, -1.0f, (float)INFINITY, (float)NAN})
+      CHECK(plan_sample(&x.b, lim, max_new, n, bad, seeds.data(), nullptr, 0, r, err) == TST_EINVAL && err.find("temperature") != std::string::npos);
+    CHECK(plan_sample(&x.b, lim, max_new, n, 0.01f, seeds.data(), nullptr, 0, r, err) == TST_OK);
+    CHECK(plan_sample(&x.b, lim, max_new, n, 100.0f, seeds.data(), nullptr, 0, r, err) == TST_OK);
+    CHECK(plan_sample(&x.b, lim, max_new, n, 1.0f, nullptr, nullptr, 0, r, err) == TST_EINVAL && err.find("seq_seeds") != std::string::npos);
+  }
+}
+
 // token attribution: the row weights / kinds of plan_attribute, its refusals, and the un-trim of the fetch side
 static void test_attribute() {
   // three sequences of 1, 2 and 5 tokens; labels on the last token of the second and on the last three of the third
@@ -534,6 +610,7 @@ static void test_lora_layout() {
 
 int main() {
   test_plan_generate();
+  test_plan_sample();
   test_attribute();
   test_ig();
   test_plan_batch();

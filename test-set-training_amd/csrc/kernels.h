@@ -195,6 +195,17 @@ template <typename AT> int attn_decode(hipStream_t st, const AT* q, long ldq, co
                                        long ldo, int H, int Hkv, int dh, float scale, long cap_rows);
 // next_token: from the rows logit_rows left in stats: tok[s, j] = argmax, logp[s, j] = max - lse, d_ids[s] = argmax, d_pos[s] = len[s] + j, lab_idx[s] = s
 int next_token(hipStream_t st, const float* stats, const int* meta, int n_seqs, int j, int* tok, float* logp, int* d_ids, int* d_pos, int* lab_idx);
+// decode.hip -- sampled generation. geo = device ints rows R | max_new | n_samples | {pre_row0, len, tail_row0} per decode row r = s n_samples + i
+// (host_logic.h plan_sample): the prompt of sequence s lies at cache rows [pre_row0, pre_row0 + len), shared by its n samples; row r's own tokens at
+// [tail_row0, tail_row0 + step). seeds = device ints {low, high 32 bits of seq_seeds[s]} per sequence.
+// attn_decode_shared: attn_decode with key k of row r at cache row k < len ? pre_row0 + k : tail_row0 + k - len; the same code path, the same bits for the same keys.
+template <typename AT> int attn_decode_shared(hipStream_t st, const AT* q, long ldq, const AT* kcache, const AT* vcache, const int* geo, int n_rows, int step,
+                                              AT* out, long ldo, int H, int Hkv, int dh, float scale, long cap_rows);
+// sample_rows: step j of a sampled generation, one pass over logits row (j == 0 ? s : r) [V of ld fp32]: tok[r, j] = first index of max_v fmaf(logit_v, inv_temp,
+// g_v) with g the Gumbel noise of Philox4x32-10 (key seeds[s], counter (v >> 2, j, i, 0), word v & 3), logp[r, j] = logit[tok] inv_temp - logsumexp(logit inv_temp),
+// d_ids[r] = tok, d_pos[r] = len + j, lab_idx[r] = r. ld a multiple of 4 and >= V rounded up to 4; the columns >= V are never candidates. Bit-reproducible.
+int sample_rows(hipStream_t st, const float* logits, long ld, int V, const int* geo, const int* seeds, int n_rows, int j, float inv_temp, int* tok, float* logp,
+                int* d_ids, int* d_pos, int* lab_idx);
 
 // One LoRA "module group" = adapters of linears that share an input (q,k,v | o | gate,up | down).
 template <typename AT>

@@ -167,3 +167,39 @@ def filter_table(src, dst, keep_ids):
         for r in kept:
             f.write(json.dumps(r, ensure_ascii=False, default=str) + "\n")
     return len(kept), len(rows) - len(kept)
+
+
+# ---- VSI-Bench's metric for numeric answers
+_NUMBER = re.compile(r"[-+]?(?:\d+(?:\.\d*)?|\.\d+)(?:[eE][-+]?\d+)?")
+
+
+def parse_number(text):
+    """the first number in a decoded answer ("about 2.5 m" -> 2.5, " 3" -> 3.0; thousands separators are not read: "1,200" -> 1.0), or None"""
+    if isinstance(text, (int, float)) and not isinstance(text, bool):
+        return float(text) if text == text and abs(text) != float("inf") else None
+    m = _NUMBER.search(str(text))
+    if m is None:
+        return None
+    try:
+        v = float(m.group(0))
+    except ValueError:
+        return None
+    return v if abs(v) != float("inf") else None
+
+
+def mean_relative_accuracy(pred, ref):
+    """VSI-Bench's mean relative accuracy of one prediction: the mean over theta in {0.50, 0.55, ..., 0.95} of 1[|pred - ref| / |ref| < 1 - theta]. pred / ref:
+    numbers or text (parse_number); an unparseable prediction scores 0, an unparseable reference raises ValueError. The comparison is exact in the decimal
+    values as written (0.9 against 1 has relative error exactly 0.1, which is not < 0.1). ref = 0 has no relative error: 1 if pred == 0, else 0."""
+    from fractions import Fraction
+    r = parse_number(ref)
+    if r is None:
+        raise ValueError(f"reference answer is not a number: {ref!r}")
+    p = parse_number(pred)
+    if p is None:
+        return 0.0
+    p, r = Fraction(repr(p)), Fraction(repr(r))
+    if r == 0:
+        return 1.0 if p == 0 else 0.0
+    rel = abs(p - r) / abs(r)
+    return sum(1 for k in range(10) if rel < Fraction(50 - 5 * k, 100)) / 10.0

@@ -88,8 +88,14 @@ def build_parser():
                        "1-rank communicators on one MI355X; a rank whose step fails aborts its communicator and exits non-zero")
         p.add_argument("--generate", action="store_true", help="also generate every held-out sample's answer (greedy, KV cache; include/tst_hip.h "
                        "tst_generate_async): the records gain gen (token ids), gen_correct and, with a tokenizer, gen_text. Off: the run is unchanged")
-        p.add_argument("--max-new-tokens", type=int, default=8, help="with --generate: tokens generated per sample (1..256)")
-        p.add_argument("--eos-ids", default=None, help="with --generate: comma-separated token ids that end an answer; default: eos_token_id of "
+        p.add_argument("--max-new-tokens", type=int, default=8, help="with --generate / --generate-samples: tokens generated per sample (1..256)")
+        p.add_argument("--generate-samples", type=int, default=0, metavar="N", help="also draw N (1..64) answers per held-out sample from the model's own "
+                       "distribution (include/tst_hip.h tst_sample_async: one prefill, N short decodes on a shared prompt cache): the records gain samples = "
+                       "{ids, logp, match (share of draws that start with the reference answer)} and, with a tokenizer, texts and mra (expected VSI-Bench mean "
+                       "relative accuracy, numeric references). Independent of --generate; uses --max-new-tokens / --eos-ids. 0: the run is unchanged")
+        p.add_argument("--temperature", type=float, default=1.0, help="with --generate-samples: sampling temperature (0.01..100); 1 is the model's distribution")
+        p.add_argument("--sample-seed", type=int, default=0, help="with --generate-samples: the run's seed; a QA pair's draws depend on it and the pair's id only")
+        p.add_argument("--eos-ids", default=None, help="with --generate / --generate-samples: comma-separated token ids that end an answer; default: eos_token_id of "
                        "<model-dir>/generation_config.json or config.json when present, else none")
         p.add_argument("--attribute", action="store_true", help="also attribute every held-out sample's score to its prompt tokens (one more forward + backward "
                        "per held-out batch; include/tst_hip.h tst_attribute_async): the records gain attr = {gxi, gnorm} over the prompt tokens and, with a "
@@ -195,6 +201,14 @@ def default_baseline_id(a):
 def _args_to_train(a):
     from .trainer import TrainArgs
     gen = dict(generate=True, max_new_tokens=int(a.max_new_tokens), eos_ids=parse_eos_ids(a)) if getattr(a, "generate", False) else {}
+    n_smp = int(getattr(a, "generate_samples", 0) or 0)
+    if n_smp != 0:
+        if not 1 <= n_smp <= 64:
+            raise SystemExit("--generate-samples must be 1..64 draws (0: off)")
+        t = float(getattr(a, "temperature", 1.0))
+        if not 0.01 <= t <= 100.0:   # (a NaN fails both)
+            raise SystemExit("--temperature must lie in [0.01, 100]")
+        gen.update(sample_n=n_smp, temperature=t, sample_seed=int(getattr(a, "sample_seed", 0) or 0), max_new_tokens=int(a.max_new_tokens), eos_ids=parse_eos_ids(a))
     if getattr(a, "attribute", False):
         if getattr(a, "dp", 1) > 1 or getattr(a, "layout", None) == "dp-stacked":
             raise SystemExit("--attribute is not available on the data-parallel layouts (--dp > 1, --layout dp-stacked)")
@@ -247,15 +261,17 @@ def _make_ctx(a, targs, local_rank, rank=0, world=1, max_answer=4):
         cfg = MODEL_SHAPES[a.model]
     bs = max(targs.per_device_train_batch_size, targs.per_device_eval_batch_size)
     L = max(128, a.max_len)
-    if targs.generate:   # room for the generated tokens behind the longest prompt: RoPE table / wpe rows (max_tokens, sized from L below, grows with it)
+    gen_on = targs.generate or targs.sample_n > 0
+    if gen_on:   # room for the generated tokens behind the longest prompt: RoPE table / wpe rows (max_tokens, sized from L below, grows with it)
         L += targs.max_new_tokens
     if a.layout == "dp-stacked":   # every rank hosts ALL k folds, laid out as one GPU would lay them out alone
         F, S, nctx = fold_layout(cfg, a.train_mode, a.k, 0, 1, a.folds_per_gpu or a.k, a.stack)
     else:
         F, S, nctx = (1, 1, 1) if a.dp > 1 else fold_layout(cfg, a.train_mode, a.k, rank, world, a.folds_per_gpu, a.stack)
-    if targs.generate and cfg.get("arch") == "gpt2" and a.max_len + targs.max_new_tokens > cfg["max_position"]:
-        raise SystemExit(f"--generate: --max-len {a.max_len} + --max-new-tokens {targs.max_new_tokens} exceeds the model's {cfg['max_position']} positions")
-    ctx = lib.Context(cfg, device=local_rank, max_tokens=bs * L * S, max_seqs=bs * S, max_labelled=max(4, max_answer) * bs * S,
+    if gen_on and cfg.get("arch") == "gpt2" and a.max_len + targs.max_new_tokens > cfg["max_position"]:
+        raise SystemExit(f"--generate / --generate-samples: --max-len {a.max_len} + --max-new-tokens {targs.max_new_tokens} exceeds the model's {cfg['max_position']} positions")
+    draws = targs.per_device_eval_batch_size * S * targs.sample_n   # every draw of a held-out batch is a decode row and a head row (0 without --generate-samples)
+    ctx = lib.Context(cfg, device=local_rank, max_tokens=max(bs * L * S, draws), max_seqs=max(bs * S, draws), max_labelled=max(max(4, max_answer) * bs * S, draws),
                       max_position=min(L, cfg["max_position"]) if cfg.get("arch") == "gpt2" else L, lora_r=targs.lora_r,
                       lora_alpha=targs.lora_alpha, lora_targets=targs.lora_targets, beta1=targs.adam_beta1, beta2=targs.adam_beta2,
                       eps=targs.adam_epsilon, weight_decay=targs.weight_decay, max_grad_norm=targs.max_grad_norm, train_mode=a.train_mode, n_stack=S)
@@ -320,7 +336,7 @@ def main(argv=None):
         samples, opt_ids = TIO.load_qa_jsonl(a.data_file, tok, max_len=a.max_len)
         targs.option_ids = tuple(opt_ids)
     decode = None
-    if targs.generate or targs.attribute_ig > 0:
+    if targs.generate or targs.attribute_ig > 0 or targs.sample_n > 0:
         tok_file = a.tokenizer or (os.path.join(a.model_dir, "tokenizer.json") if a.model_dir else None)
         if tok_file and os.path.exists(tok_file):
             from tokenizers import Tokenizer

@@ -7,6 +7,10 @@ held-out sample); that file is the checkpoint/resume unit (a crashed worker's fo
     {"id": int, "fold": int, "round": int, "s": float, "pred": int, "correct": int, "kind": "mca"|"na"}
 With TrainArgs.generate every record also carries what the text-only model answers: "gen" (the greedy continuation of the prompt, token ids without the
 eos token), "gen_correct" (it starts with the reference answer's ids) and, when the caller hands a `decode` function (the CLI: its tokenizer), "gen_text".
+With TrainArgs.sample_n > 0 every record also carries the distribution of those answers: "samples" = {"ids": sample_n id lists (draws from the model's
+distribution at TrainArgs.temperature, include/tst_hip.h tst_sample_async, without the eos token), "logp": their summed log-probabilities, "match": the share of
+draws that start with the reference answer's ids} and, with a `decode` function, "texts" and -- where the reference answer reads as a number -- "mra", the mean
+over the draws of VSI-Bench's mean relative accuracy. A QA pair's draws depend on TrainArgs.sample_seed and the pair's id only.
 With TrainArgs.attribute every record also carries which prompt tokens its score rests on: "attr" = {"gxi": [...], "gnorm": [...]} over the prompt tokens
 (gradient x input and gradient norm of log s(x) per token, include/tst_hip.h tst_attribute_async) and, with a `decode` function, "attr_top": the
 TrainArgs.attribute_top tokens of largest gnorm, as text. Not available on the data-parallel layouts.
@@ -23,11 +27,12 @@ import time
 import numpy as np
 
 from . import kfold
-from .trainer import (ATTRIBUTE, GENERATE, IG, SCORE, TrainArgs, fine_tune, fine_tune_concurrent, fine_tune_dp, fine_tune_stacked, run_heldout,
+from .trainer import (ATTRIBUTE, GENERATE, IG, SAMPLE, SCORE, TrainArgs, fine_tune, fine_tune_concurrent, fine_tune_dp, fine_tune_stacked, run_heldout,
                       run_heldout_concurrent, run_heldout_stacked)
 
 GEN_ARGS = ("generate", "max_new_tokens", "eos_ids")   # TrainArgs fields that enter the run fingerprint only when generation is on
 ATTR_ARGS = ("attribute", "attribute_top")             # TrainArgs settings that enter it only when attribution is on
+SAMPLE_ARGS = ("sample_n", "temperature", "sample_seed")   # likewise, when sampled answers are on (max_new_tokens / eos_ids then enter too: they shape the draws)
 IG_ARGS = ("attribute_ig", "attribute_baseline_id")    # likewise, when integrated gradients are on (attribute_top then enters too: it sizes attr_ig_top)
 
 
@@ -39,6 +44,7 @@ def run_fingerprint(samples, k, args, extra=None):
     import hashlib
     h = hashlib.sha256()
     a = dataclasses.asdict(args) if dataclasses.is_dataclass(args) else dict(args)
+    kept = {kk: a[kk] for kk in GEN_ARGS[1:] if kk in a}
     if not a.get("generate"):   # a run without generation is the run it was before the option existed: its directory still resumes
         for kk in GEN_ARGS:
             a.pop(kk, None)
@@ -51,6 +57,12 @@ def run_fingerprint(samples, k, args, extra=None):
         a.update({kk: getattr(args, kk) for kk in IG_ARGS + ("attribute_top",)})
     else:
         for kk in IG_ARGS:
+            a.pop(kk, None)
+    if int(getattr(args, "sample_n", 0) or 0) > 0:
+        a.update({kk: getattr(args, kk) for kk in SAMPLE_ARGS})
+        a.update(kept)
+    else:
+        for kk in SAMPLE_ARGS:
             a.pop(kk, None)
     h.update(json.dumps(dict(args={kk: (list(v) if isinstance(v, tuple) else v) for kk, v in sorted(a.items())}, k=int(k), n=len(samples),
                              extra=extra or {}), sort_keys=True).encode())
@@ -100,18 +112,20 @@ def train_health(recs):
 
 
 def heldout_passes(layout, ctxs, helds, args: TrainArgs):
-    """score, then every enabled extra pass (generate, attribute, ig: in this order) over the held-out folds. layout: "one" (ctxs is one context, helds one fold),
-    "concurrent" (a context per fold) or "stacked". Per fold: ((s, pred, correct), extras), extras = {"gen" / "attr" / "ig": per-sample results} of what ran."""
+    """score, then every enabled extra pass (generate, sample, attribute, ig: in this order) over the held-out folds. layout: "one" (ctxs is one context, helds one fold),
+    "concurrent" (a context per fold) or "stacked". Per fold: ((s, pred, correct), extras), extras = {"gen" / "samples" / "attr" / "ig": per-sample results} of what ran."""
     run = dict(one=lambda p, c, sets, a: [run_heldout(p, c, sets[0], a)], concurrent=run_heldout_concurrent, stacked=run_heldout_stacked)[layout]
     scored = run(SCORE, ctxs, helds, args)
-    enabled = (("gen", GENERATE, args.generate), ("attr", ATTRIBUTE, args.attribute), ("ig", IG, args.attribute_ig > 0))
+    enabled = (("gen", GENERATE, args.generate), ("samples", SAMPLE, getattr(args, "sample_n", 0) > 0), ("attr", ATTRIBUTE, args.attribute),
+               ("ig", IG, args.attribute_ig > 0))
     ran = {key: run(p, ctxs, helds, args) for key, p, on in enabled if on}
     return [(sc, {key: got[i] for key, got in ran.items()}) for i, sc in enumerate(scored)]
 
 
-def fold_records(held, f, rnd, s, pred, correct, decode=None, attr_top=5, *, gen=None, attr=None, ig=None):
+def fold_records(held, f, rnd, s, pred, correct, decode=None, attr_top=5, *, gen=None, attr=None, ig=None, samples=None):
     """the records of one scored held-out fold; decode = ids -> text; the extras (heldout_passes' mapping, as keywords): gen = [(gen ids, gen_correct)] per sample
-    when generation is on, attr = tst.score.token_attribution's dict when attribution is on, ig = tst.score.token_ig's when integrated gradients are"""
+    when generation is on, samples = tst.score.sampled_answers' dict when sampled answers are, attr = tst.score.token_attribution's dict when attribution is on,
+    ig = tst.score.token_ig's when integrated gradients are"""
     records = [dict(id=int(x.sid), fold=int(f), round=int(rnd), s=float(si), pred=int(pi), correct=int(ci), kind=x.kind)
                for x, si, pi, ci in zip(held, s, pred, correct)]
     if gen is not None:
@@ -120,6 +134,18 @@ def fold_records(held, f, rnd, s, pred, correct, decode=None, attr_top=5, *, gen
             r["gen_correct"] = int(gc)
             if decode is not None:
                 r["gen_text"] = decode(r["gen"])
+    if samples is not None:
+        # samples = tst.score.sampled_answers' dict: the draws' ids, their summed log-probabilities and the share that starts with the reference answer; with a
+        # tokenizer their texts, and for a reference answer that reads as a number the expected mean relative accuracy over the draws
+        from .benchmarks import mean_relative_accuracy, parse_number
+        for r, x, sm in zip(records, held, samples):
+            r["samples"] = dict(ids=[[int(t) for t in g] for g in sm["ids"]], logp=[float(v) for v in sm["logp"]], match=float(sm["match"]))
+            if decode is not None:
+                texts = [decode(g) for g in r["samples"]["ids"]]
+                r["samples"]["texts"] = texts
+                ref = decode([int(t) for t in x.ids[x.n_prompt:]])
+                if parse_number(ref) is not None and texts:
+                    r["samples"]["mra"] = float(np.mean([mean_relative_accuracy(t, ref) for t in texts]))
     if attr is not None:
         for r, x, a in zip(records, held, attr):
             r["attr"] = dict(gxi=[float(v) for v in a["gxi"]], gnorm=[float(v) for v in a["gnorm"]])

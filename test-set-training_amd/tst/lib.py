@@ -135,6 +135,9 @@ SIGNATURES = {
     "tst_generate_async": (C.c_int, [_P, C.POINTER(Batch), C.c_int32, _P, C.c_int32]),
     "tst_generate_fetch": (C.c_int, [_P, _P, _P, _P]),
     "tst_generate": (C.c_int, [_P, C.POINTER(Batch), C.c_int32, _P, C.c_int32, _P, _P, _P]),
+    "tst_sample_async": (C.c_int, [_P, C.POINTER(Batch), C.c_int32, C.c_int32, _F, _P, _P, C.c_int32]),
+    "tst_sample_fetch": (C.c_int, [_P, _P, _P, _P]),
+    "tst_sample": (C.c_int, [_P, C.POINTER(Batch), C.c_int32, C.c_int32, _F, _P, _P, C.c_int32, _P, _P, _P]),
     "tst_attribute_async": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.c_int32]),
     "tst_attribute_fetch": (C.c_int, [_P, _P, _P, _P]),
     "tst_attribute": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.c_int32, _P, _P, _P]),
@@ -196,6 +199,9 @@ LAB_SIGNATURES = {
     "tst_k_attn_bwd_rope": (C.c_int, [_P, _L, _P, _L, _P, _L, _P, _P, _P, _I, _I, _P, _I, _I, _I, _I, _F, _P, _P]),
     "tst_k_kv_append": (C.c_int, [_P, _L, _I, _P, _P, _P, _I, _I, _I, _L]),
     "tst_k_attn_decode": (C.c_int, [_P, _L, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _F, _L]),
+    "tst_k_attn_decode_shared": (C.c_int, [_P, _L, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _F, _L]),
+    "tst_k_attn_decode_shared_f32": (C.c_int, [_P, _L, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _F, _L]),
+    "tst_k_sample_rows": (C.c_int, [_P, _L, _I, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P]),
     "tst_k_kv_append_f32": (C.c_int, [_P, _L, _I, _P, _P, _P, _I, _I, _I, _L]),
     "tst_k_attn_decode_f32": (C.c_int, [_P, _L, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _F, _L]),
     "tst_k_adamw": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _I, _P, _P]),
@@ -237,6 +243,7 @@ HOST_SIGNATURES = {
     "tst_host_stage_ints": (_L, [_P]),
     "tst_host_plan_batch": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I]),
     "tst_host_plan_generate": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I]),
+    "tst_host_plan_sample": (C.c_int, [_P, _P, _I, _I, _F, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I]),
     "tst_host_cut_at_eos": (C.c_int, [_P, _P, _P, _I, _I, _P, _I]),
     "tst_host_plan_attribute": (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I]),
     "tst_host_untrim_tokens": (C.c_int, [_P, _P, _P, _I, _P]),
@@ -388,6 +395,39 @@ def host_plan_generate(mc, ids, cu, max_new, eos_ids=(), seq_slot=None):
         raise TstError(err.value.decode() or f"tst_host_plan_generate rc={rc}")
     return dict(S=int(out[0]), T=int(out[1]), rows_used=int(out[2]), cache_rows=int(out[3]), slot_s_end=out[4:12].astype(np.int32), meta=meta, last_rows=last[:S],
                 prefill_rows=pre[:T], decode_rows=dec[:(int(max_new) - 1) * S].reshape(int(max_new) - 1, S))
+
+
+SAMPLE_MAX_N = 64   # tsthost::kSampleMaxN
+
+
+def host_plan_sample(mc, ids, cu, max_new, n_samples, temperature, seq_seeds, eos_ids=(), seq_slot=None):
+    """tsthost::plan_sample through the CPU library: dict(S, T, R, rows_used, cache_rows, dev_ints, dev_ints_alloc, slot_r_end, geo [3 + 3 R], seeds [S, 2] (low,
+    high word), last_rows, prefill_rows, decode_rows [max_new - 1, R]); seq_seeds = None passes a NULL pointer; raises TstError with the library's message for a
+    refused call"""
+    L = load_host()
+    ids = np.ascontiguousarray(ids, np.int32)
+    cu = np.ascontiguousarray(cu, np.int32)
+    sl = None if seq_slot is None else np.ascontiguousarray(seq_slot, np.int32)
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    S, T = len(cu) - 1, len(ids)
+    b = Batch(ip(ids), None, ip(cu), S, T, ip(sl), 0)
+    eos = np.ascontiguousarray(eos_ids, np.int32)
+    seeds_in = None if seq_seeds is None else np.ascontiguousarray(seq_seeds, np.uint64)
+    if seeds_in is not None and len(seeds_in) != S:
+        raise TstError("seq_seeds needs one seed per sequence")
+    n_cl, m_cl = min(max(int(n_samples), 1), SAMPLE_MAX_N), min(max(int(max_new), 1), GEN_MAX_NEW)
+    R = max(S, 0) * n_cl
+    out, err = np.zeros(15, np.int64), C.create_string_buffer(256)
+    geo, seeds, last, pre = np.zeros(3 + 3 * R, np.int32), np.zeros(max(2 * S, 2), np.int32), np.zeros(max(S, 1), np.int32), np.zeros(max(T, 1), np.int32)
+    dec = np.zeros(max(1, (m_cl - 1) * R), np.int32)
+    rc = L.tst_host_plan_sample(C.byref(mc), C.byref(b), int(max_new), int(n_samples), float(temperature), None if seeds_in is None else _ptr(seeds_in),
+                                _ptr(eos) if len(eos) else None, len(eos), _ptr(out), _ptr(geo), _ptr(seeds), _ptr(last), _ptr(pre), _ptr(dec), err, 256)
+    if rc != 0:
+        raise TstError(err.value.decode() or f"tst_host_plan_sample rc={rc}")
+    R = int(out[2])
+    return dict(S=int(out[0]), T=int(out[1]), R=R, rows_used=int(out[3]), cache_rows=int(out[4]), dev_ints=int(out[5]), dev_ints_alloc=int(out[6]),
+                slot_r_end=out[7:15].astype(np.int32), geo=geo[:3 + 3 * R], seeds=seeds[:2 * S].reshape(S, 2), last_rows=last[:S], prefill_rows=pre[:T],
+                decode_rows=dec[:(int(max_new) - 1) * R].reshape(int(max_new) - 1, R))
 
 
 def host_cut_at_eos(tokens, logp, eos_ids):
@@ -974,6 +1014,32 @@ class Context:
     def generate(self, ids, cu, max_new_tokens, eos_ids=(), seq_slot=None):
         self.generate_async(ids, cu, max_new_tokens, eos_ids, seq_slot)
         return self.generate_fetch()
+
+    # ---- sampled generation (include/tst_hip.h tst_sample_async)
+    def sample_async(self, ids, cu, max_new_tokens, n_samples, temperature, seq_seeds, eos_ids=(), seq_slot=None):
+        """enqueue n_samples draws of max_new_tokens tokens from softmax(logits / temperature) for every packed prompt (ids, cu), at one prefill; seq_seeds = one
+        uint64 per prompt (a prompt's draws depend on its logits, its seed, the step and the sample index only). Results come from sample_fetch()."""
+        b, keep = self._batch(ids, None, cu, seq_slot)
+        n_seqs = len(keep[2]) - 1
+        seeds = np.ascontiguousarray(seq_seeds, np.uint64).reshape(-1)
+        if len(seeds) != n_seqs:
+            raise TstError("seq_seeds needs one seed per sequence")
+        eos_a, _ = _i32(np.asarray(eos_ids, np.int32) if len(eos_ids) else np.zeros(1, np.int32))
+        self._check(self.lib.tst_sample_async(self.h, C.byref(b), int(max_new_tokens), int(n_samples), float(temperature), _ptr(seeds), _ptr(eos_a), len(eos_ids)),
+                    "tst_sample_async")
+        self._pending_sample = (n_seqs, int(n_samples), int(max_new_tokens))
+
+    def sample_fetch(self):
+        """(tokens [n_seqs, n_samples, max_new] int32, logp (same shape), n_new [n_seqs, n_samples]): every draw is cut behind its first eos token (-1 / 0 behind it)"""
+        s, n, m = getattr(self, "_pending_sample", None) or (1, 1, 1)
+        tok, logp, n_new = np.full((s, n, m), -1, np.int32), np.zeros((s, n, m), np.float32), np.zeros((s, n), np.int32)
+        self._check(self.lib.tst_sample_fetch(self.h, _ptr(tok), _ptr(logp), _ptr(n_new)), "tst_sample_fetch")
+        self._pending_sample = None
+        return tok, logp, n_new
+
+    def sample(self, ids, cu, max_new_tokens, n_samples, temperature, seq_seeds, eos_ids=(), seq_slot=None):
+        self.sample_async(ids, cu, max_new_tokens, n_samples, temperature, seq_seeds, eos_ids, seq_slot)
+        return self.sample_fetch()
 
     # ---- token attribution (include/tst_hip.h tst_attribute_async)
     def attribute_async(self, ids, labels, cu, seq_kind=None, option_ids=(), seq_slot=None):

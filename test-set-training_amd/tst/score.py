@@ -104,3 +104,41 @@ def generated_answers(samples, tokens, n_new, eos_ids=()):
         ans = [int(t) for t in smp.ids[smp.n_prompt:]]
         out.append((gen, int(len(ans) > 0 and gen[:len(ans)] == ans)))
     return out
+
+
+_M64 = (1 << 64) - 1
+
+
+def sample_seeds(sample_seed, dataset_indices):
+    """one uint64 per QA pair for Context.sample's seq_seeds: output number (index + 1) of the splitmix64 generator seeded with the run's sample_seed, i.e. the
+    splitmix64 finaliser of sample_seed + (index + 1) * 0x9E3779B97F4A7C15 mod 2^64. It depends on the run's seed and the pair's index in the data set and on
+    nothing else, so a pair's draws are the same function of its logits in every fold layout, batch order and stacking."""
+    out = np.zeros(len(dataset_indices), np.uint64)
+    for k, idx in enumerate(dataset_indices):
+        z = (int(sample_seed) + (int(idx) + 1) * 0x9E3779B97F4A7C15) & _M64
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+        out[k] = z ^ (z >> 31)
+    return out
+
+
+def sampled_answers(samples, tokens, logp, n_new, eos_ids=()):
+    """samples: the prompts' samples in batch order; tokens / logp [n, n_samples, max_new] and n_new [n, n_samples] as returned by Context.sample (every draw cut
+    behind its first eos token). Returns per sample dict(ids = the n_samples id lists without the eos token, logp = the summed log-probability of each draw (its
+    eos token included: the probability of the whole answer at the sampling temperature), match = the share of draws whose first n_answer ids equal the reference
+    answer ids)."""
+    eos = set(int(e) for e in eos_ids)
+    out = []
+    for i, smp in enumerate(samples):
+        ans = [int(t) for t in smp.ids[smp.n_prompt:]]
+        ids, lps, hit = [], [], 0
+        for k in range(np.asarray(tokens).shape[1]):
+            m = int(n_new[i][k])
+            gen = [int(t) for t in np.asarray(tokens[i][k])[:m]]
+            lps.append(float(np.asarray(logp[i][k], np.float64)[:m].sum()))
+            if gen and gen[-1] in eos:
+                gen = gen[:-1]
+            ids.append(gen)
+            hit += int(len(ans) > 0 and gen[:len(ans)] == ans)
+        out.append(dict(ids=ids, logp=lps, match=hit / max(len(ids), 1)))
+    return out

@@ -50,10 +50,17 @@ class TrainArgs:
     # NOT dataclass fields, for the reason above.
     attribute_ig: InitVar[int] = 0
     attribute_baseline_id: InitVar[int] = 0
+    # sampled answers on the held-out fold (off at 0 samples): every record gains `samples`, sample_n draws of max_new_tokens tokens from the model's own
+    # distribution at `temperature` (include/tst_hip.h tst_sample_async; eos_ids end a draw), seeded per QA pair from sample_seed and the pair's id
+    # (tst.score.sample_seeds). Independent of `generate`. Constructor arguments and attributes, NOT dataclass fields, for the reason above.
+    sample_n: InitVar[int] = 0
+    temperature: InitVar[float] = 1.0
+    sample_seed: InitVar[int] = 0
 
-    def __post_init__(self, attribute, attribute_top, attribute_ig, attribute_baseline_id):
+    def __post_init__(self, attribute, attribute_top, attribute_ig, attribute_baseline_id, sample_n, temperature, sample_seed):
         self.attribute, self.attribute_top = bool(attribute), int(attribute_top)
         self.attribute_ig, self.attribute_baseline_id = int(attribute_ig), int(attribute_baseline_id)
+        self.sample_n, self.temperature, self.sample_seed = int(sample_n), float(temperature), int(sample_seed)
 
 
 def linear_lr(step, total, lr0, warmup=0):
@@ -208,6 +215,16 @@ def _generate_fetch(ctx, batch, args):
     return S.generated_answers(batch, tok, n_new, args.eos_ids)
 
 
+def _sample_enqueue(ctx, batch, args, *seq_slot):
+    ids, cu = collate_prompts(batch)
+    ctx.sample_async(ids, cu, args.max_new_tokens, args.sample_n, args.temperature, S.sample_seeds(args.sample_seed, [x.sid for x in batch]), args.eos_ids, *seq_slot)
+
+
+def _sample_fetch(ctx, batch, args):
+    tok, logp, n_new = ctx.sample_fetch()
+    return S.sampled_answers(batch, tok, logp, n_new, args.eos_ids)
+
+
 def _attribute_enqueue(ctx, batch, args, *seq_slot):
     ids, labels, cu = D.collate(batch)
     ctx.attribute_async(ids, labels, cu, S.attribution_kinds(batch), args.option_ids, *seq_slot)   # MCA and open samples in one batch
@@ -223,6 +240,9 @@ def _ig_enqueue(ctx, batch, args, *seq_slot):
 SCORE = HeldoutPass(_score_enqueue, lambda ctx, batch, args: list(zip(*S.bias_scores(batch, *ctx.score_rows_fetch()))), _score_join)
 # greedy continuation of every prompt by args.max_new_tokens tokens: [(gen ids, gen_correct)] (tst.score.generated_answers)
 GENERATE = HeldoutPass(_generate_enqueue, _generate_fetch, list)
+# args.sample_n draws per prompt from softmax(logits / args.temperature), one prefill per batch: tst.score.sampled_answers' dict per sample. A pair's draws depend
+# on args.sample_seed and its id only, not on the fold layout, the batch or the slot
+SAMPLE = HeldoutPass(_sample_enqueue, _sample_fetch, list)
 # input-gradient attribution of log s(x): tst.score.token_attribution's dict per sample. About one training forward + backward per batch.
 ATTRIBUTE = HeldoutPass(_attribute_enqueue, lambda ctx, batch, args: S.token_attribution(batch, *ctx.attribute_fetch()), list)
 # integrated gradients of log s(x), args.attribute_ig steps from a prompt of args.attribute_baseline_id: tst.score.token_ig's dict per sample.
@@ -307,6 +327,11 @@ def score_heldout(ctx, samples, args: TrainArgs):
 def generate_heldout(ctx, samples, args: TrainArgs):
     """greedy continuation of every held-out prompt; returns [(gen ids, gen_correct)] per sample in input order."""
     return run_heldout(GENERATE, ctx, samples, args)
+
+
+def sample_heldout(ctx, samples, args: TrainArgs):
+    """args.sample_n sampled continuations of every held-out prompt; returns tst.score.sampled_answers' dict per sample in input order."""
+    return run_heldout(SAMPLE, ctx, samples, args)
 
 
 def attribute_heldout(ctx, samples, args: TrainArgs):
