@@ -387,6 +387,36 @@ int tst_sample_fetch(tst_ctx* ctx, int32_t* tokens_out /* [n_seqs, n_samples, ma
 int tst_sample(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, int32_t n_samples, float temperature, const uint64_t* seq_seeds, const int32_t* eos_ids,
                int32_t n_eos, int32_t* tokens_out, float* logp_out, int32_t* n_new_out);
 
+/* ---- candidate scoring: exact log p(candidate | prompt) for given continuations, at one prefill ----
+ * Candidate c = the tokens cand_ids[cu_cand[c] .. cu_cand[c + 1]) (1 .. TST_CAND_MAX_LEN of them, host memory) continues prompt cand_seq[c] of the packed
+ * prompts of b (labels ignored; seq_slot and TST_BATCH_DEVICE_IDS as for tst_score_async); cand_seq is non-decreasing, a prompt without candidates is prefilled
+ * and nothing more. For candidate c = c_0 .. c_{L-1} behind a prompt of len tokens
+ *   logp_tok_out[cu_cand[c] + p] = log softmax(logits(prompt, c_0 .. c_{p-1}))[c_p]       (teacher-forced, temperature 1)
+ *   logp_cand_out[c]             = their sum, formed on the host in double in token order and rounded once.
+ * tst_score_candidates_async enqueues, without a host wait in between: ONE prefill over the prompts (cache rows 0 .. n_tokens; the head on the n_seqs last
+ * rows -- every candidate's first token is read from its prompt's one logits row), then ONE forward pass over the R_e = sum_c (L_c - 1) "extend rows"
+ * (candidate c, position p), p = 0 .. L_c - 2, c-major: row (c, p) is fed c_p at position len + p, its k | v join the cache at row n_tokens + (cu_cand[c] - c) + p
+ * (the tails packed behind the prompts), attention is ONE launch per layer over all positions of all candidates (csrc/decode.hip attn_extend, bit-identical per
+ * position to the decode step of a sampled generation), and the head runs on all R_e rows with targets c_{p+1}.
+ * Available wherever tst_generate_async is; it reads weights and adapters only: trainables, gradients, optimizer state, an open accumulation window, a pending
+ * scoring pass and a pending attribution are left as they are. It uses the generation's cache and pending slot: ONE of tst_generate_async, tst_sample_async and
+ * tst_score_candidates_async may be pending per context; a fetch of another kind, or without a pending call, returns TST_ESTATE, and a mismatched fetch leaves
+ * the pending call pending.
+ * Memory: the cache of a one-token generation (max_tokens + max_seqs rows; a larger one a generation left is used as it is) under the generation's allocation
+ * rule, and on the first call a device image / output block of its own (4 bytes x (6 min(max_tokens, max_seqs, max_labelled) + 3 max_labelled)), counted in
+ * tst_device_bytes and freed with the context; forks own theirs. A context that never calls it allocates what it did before.
+ * TST_EINVAL before anything is allocated or launched (tst_last_error names the reason; tst_device_bytes is unchanged): the batch's own checks as for
+ * tst_generate_async; n_cands < 1; cu_cand not strictly increasing from 0; a candidate longer than TST_CAND_MAX_LEN; a candidate id outside the vocabulary;
+ * cand_seq outside 0 .. n_seqs - 1 or decreasing; len + L_c - 1 > max_position; more candidate tokens than max_labelled; R_e > min(max_tokens, max_seqs,
+ * max_labelled) (the extend pass is a forward over R_e one-token rows, as a sampled decode step is over its draws); n_seqs > max_labelled; the head_dim /
+ * heads-per-kv-head restriction of generation. */
+#define TST_CAND_MAX_LEN 16
+int tst_score_candidates_async(tst_ctx* ctx, const tst_batch* b, const int32_t* cand_ids /* [n_cand_tokens] */, const int32_t* cu_cand /* [n_cands + 1] */,
+                               const int32_t* cand_seq /* [n_cands] */, int32_t n_cands);
+int tst_score_candidates_fetch(tst_ctx* ctx, float* logp_tok_out /* [n_cand_tokens] */, float* logp_cand_out /* [n_cands] */);
+int tst_score_candidates(tst_ctx* ctx, const tst_batch* b, const int32_t* cand_ids, const int32_t* cu_cand, const int32_t* cand_seq, int32_t n_cands,
+                         float* logp_tok_out, float* logp_cand_out);
+
 /* ---- token attribution: input-gradient saliency of s(x) ----
  * Which tokens of a sequence carry its score. Position p predicts labels[p + 1]; rows(i) = the labelled rows of sequence i, n_i their number, z_r the fp32
  * logits of row r. Per sequence (seq_kind[i]; NULL = all 0):

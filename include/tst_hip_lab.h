@@ -144,6 +144,16 @@ int tst_k_attn_decode_shared_f32(const void* q, int64_t ldq, const void* kcache,
                                  int64_t ldo, int H, int Hkv, int dh, float scale, int64_t cap_rows);
 int tst_k_sample_rows(const float* logits, int64_t ld, int V, const int32_t* geo, const int32_t* seeds, int n_rows, int j, float inv_temp, int32_t* tok, float* logp,
                       int32_t* d_ids, int32_t* d_pos, int32_t* lab_idx);
+/* candidate-scoring kernels (csrc/decode.hip). geo = device int32 {pre_row0, len, tail_row0, q_row0, n_pos} per candidate with at least two tokens.
+ * attn_extend: rows q_row0 .. q_row0 + n_pos - 1 of out (n_rows rows, as q) = attention of the query in the same row of q over the keys 0 .. len + p, key k at
+ * cache row k < len ? pre_row0 + k : tail_row0 + k - len; per (position, head) bit-identical to attn_decode_shared at step = p + 1.
+ * cand_logp: out[t], t < n, from src = {row, tok} per candidate token: phase 0 writes logits[row, tok] - stats[row, 0] where tok >= 0, phase 1 writes
+ * stats[row, 1] - stats[row, 0] where tok < 0; stats = fp32 [n_rows, 4] as logit_rows leaves it. */
+int tst_k_attn_extend(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* geo, int n_cands, int n_rows, void* out, int64_t ldo, int H,
+                      int Hkv, int dh, float scale, int64_t cap_rows);
+int tst_k_attn_extend_f32(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* geo, int n_cands, int n_rows, void* out, int64_t ldo,
+                          int H, int Hkv, int dh, float scale, int64_t cap_rows);
+int tst_k_cand_logp(const float* logits, int64_t ld, int V, const float* stats, int n_rows, const int32_t* src, int n, int phase, float* out);
 int tst_k_adamw(float* p, const float* g, float* m, float* v, int64_t n, float max_norm, float lr, float beta1, float beta2, float eps, float wd,
                 int step, float* norm_coef_out /* device [2] */, float* partial_ws /* device [256] */);
 /* the optimizer kernels of csrc/optim.hip one by one; every pointer is a device pointer unless stated, every hook synchronises.

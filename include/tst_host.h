@@ -60,6 +60,14 @@ int tst_host_plan_generate(const tst_model_cfg* cfg, const tst_batch* b, int max
 int tst_host_plan_sample(const tst_model_cfg* cfg, const tst_batch* b, int max_new, int n_samples, float temperature, const uint64_t* seq_seeds,
                          const int32_t* eos_ids, int n_eos, int64_t* out_ints, int32_t* geo_out, int32_t* seeds_out, int32_t* last_rows_out, int32_t* prefill_rows_out,
                          int32_t* decode_rows_out, char* err_out, int err_cap);
+/* tsthost::plan_candidates (candidate scoring, include/tst_hip.h tst_score_candidates_async): every refusal of that call but the host ids of the prompts, and
+ * the extend row map. out_ints[8 + 8] = {S, T, n_cand_tokens, R_e, candidates with at least two tokens, cache rows used (T + R_e), cache rows the context
+ * allocates (max_tokens + max_seqs), ints of the call's device image at capacity, slot_r_end[8]}; geo_out [5 n_ext] ({pre_row0, len, tail_row0, q_row0, n_pos} per
+ * candidate with at least two tokens), ext_rows_out / ext_ids_out / ext_pos_out / ext_tgt_out [R_e], src_out [2 n_cand_tokens] ({row, tok} per candidate token:
+ * {prompt, c_0} for a first token, {extend row, -1} for a later one), last_rows_out [S] may each be NULL. Returns TST_OK or TST_EINVAL. */
+int tst_host_plan_candidates(const tst_model_cfg* cfg, const tst_batch* b, const int32_t* cand_ids, const int32_t* cu_cand, const int32_t* cand_seq, int n_cands,
+                             int64_t* out_ints, int32_t* geo_out, int32_t* ext_rows_out, int32_t* ext_ids_out, int32_t* ext_pos_out, int32_t* ext_tgt_out,
+                             int32_t* src_out, int32_t* last_rows_out, char* err_out, int err_cap);
 /* the fetch side of a generation: rows of tokens / logp [n_seqs, max_new] are cut behind their first token that is in eos_ids (tokens -1, logp 0 behind it;
  * n_new_out[s] counts the eos token), in place */
 int tst_host_cut_at_eos(int32_t* tokens, float* logp, int32_t* n_new_out, int n_seqs, int max_new, const int32_t* eos_ids, int n_eos);

@@ -17,6 +17,10 @@
 //   sample_rows          logit_rows + next_token of a sampled step in ONE pass over the logits row: the log-sum-exp of logit / temperature and a Gumbel-max
 //                        draw from softmax(logits / temperature), noise from Philox4x32-10
 //
+// Candidate scoring (tst_score_candidates_async) adds two:
+//   attn_extend          attn_decode, SHARED for ALL positions of a given continuation at once: the register sets hold (position, query head) pairs
+//   cand_logp            log p of every candidate token from the prefill's logits (first tokens) and the extend pass's row statistics (the rest)
+//
 // The generation's geometry travels in one small device array `meta` (host_logic.h plan_generate writes it):
 //   meta[0] = n_seqs S, meta[1] = max_new, meta[2 .. 2 + S] = cu_seqlens of the prompts, meta[3 + S .. 3 + 2 S) = their lengths.
 // Cache row of (sequence s, position p) = cu[s] + s max_new + p: the packed prompts with room for max_new tokens behind each.
@@ -307,6 +311,153 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const float* __restric
   }
 }
 
+// ---- candidate scoring (tst_score_candidates_async): every position of a given continuation in ONE launch per layer. geo = {pre_row0, len, tail_row0, q_row0,
+// n_pos} per candidate with at least two tokens (host_logic.h plan_candidates): the prompt lies at cache rows [pre_row0, pre_row0 + len), the candidate's own
+// tokens 0 .. n_pos - 1 at [tail_row0, tail_row0 + n_pos), their queries at rows q_row0 .. q_row0 + n_pos - 1 of q / out. The GP register sets of attn_decode hold
+// (position, query head) pairs: set e = pl Gpad + g (Gpad = 1 << gsh, G rounded up to 1, 2, 4, 8), so one pass over the keys serves P = GP / Gpad consecutive
+// positions; pair (p, g) takes the keys 0 .. len + p and skips the later ones. Per pair the keys a row group sees, their order, the products and every merge are
+// those of attn_decode_kernel<.., SHARED> at step = p + 1: the same bits.
+template <typename AT, int DH, int GP>
+__global__ __launch_bounds__(256) void attn_extend_kernel(const AT* __restrict__ q, long ldq, const AT* __restrict__ kcache, const AT* __restrict__ vcache,
+                                                          const int* __restrict__ geo, int n_rows, AT* __restrict__ out, long ldo, int G, int gsh, int Hkv, float scale,
+                                                          long cap_rows) {
+  constexpr int LPR = DH / 8;     // lanes per cache row
+  constexpr int NG = 256 / LPR;   // row groups per workgroup
+  typedef typename MergeT<AT>::type MT;
+  __shared__ MT red[4][GP][LPR * 8 + 2];
+  const int c = blockIdx.x, kvh = blockIdx.y;
+  const long row0 = geo[5 * c];
+  const int len = geo[5 * c + 1];
+  const long tail0 = geo[5 * c + 2], q0 = geo[5 * c + 3];
+  const int n_pos = geo[5 * c + 4];
+  // (plan_candidates keeps the prompt, every tail and every query row in range: never taken)
+  if (len <= 0 || n_pos < 1 || row0 < 0 || row0 + len > cap_rows || tail0 < 0 || tail0 + n_pos > cap_rows || q0 < 0 || q0 + n_pos > n_rows) return;
+  const int tid = threadIdx.x, sub = tid % LPR, grp = tid / LPR;
+  const int wkv = Hkv * DH;
+  const int P = GP >> gsh, gmask = (1 << gsh) - 1;
+  const AT* kp = kcache + row0 * wkv + (long)kvh * DH + sub * 8;
+  const AT* vp = vcache + row0 * wkv + (long)kvh * DH + sub * 8;
+  auto key_off = [&](int k) -> long { return (k < len ? (long)k : tail0 - row0 + (k - len)) * wkv; };
+  const MT NEG_INF = (MT)(-INFINITY);
+  for (int p0 = 0; p0 < n_pos; p0 += P) {
+    float qf[GP][8], acc[GP][8], m[GP], l[GP];
+    int ne[GP];   // keys of set e (0: the set is empty -- a padded head, or a position behind the candidate's last)
+#pragma unroll
+    for (int e = 0; e < GP; ++e) {
+      const int pl = e >> gsh, g = e & gmask;
+      ne[e] = (g < G && p0 + pl < n_pos) ? len + p0 + pl + 1 : 0;
+      m[e] = -INFINITY;
+      l[e] = 0.f;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) { acc[e][i] = 0.f; qf[e][i] = 0.f; }
+      if (ne[e]) ld8(q + (q0 + p0 + pl) * ldq + (long)(kvh * G + g) * DH + sub * 8, qf[e]);
+    }
+    const int n = len + (p0 + P < n_pos ? p0 + P : n_pos);   // keys of the pass's last position
+    auto one_key = [&](int j, const float* kf, const float* vf) {
+#pragma unroll
+      for (int e = 0; e < GP; ++e) {
+        if (j < ne[e]) {
+          float d = 0.f;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) d = __builtin_fmaf(qf[e][i], kf[i], d);
+          const float sc = rowgroup_sum<LPR>(d) * scale;
+          const float mn = fmaxf(m[e], sc);
+          const float corr = exp_of<AT>(m[e] - mn);
+          const float p = exp_of<AT>(sc - mn);
+          l[e] = __builtin_fmaf(l[e], corr, p);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) acc[e][i] = __builtin_fmaf(p, vf[i], acc[e][i] * corr);
+          m[e] = mn;
+        }
+      }
+    };
+    // two keys per trip, as attn_decode: row group r takes the keys r, r + NG, .. in ascending order
+    for (int j = grp; j < n; j += 2 * NG) {
+      float k0[8], v0[8], k1[8], v1[8];
+      const bool two = j + NG < n;
+      ld8(kp + key_off(j), k0);
+      ld8(vp + key_off(j), v0);
+      if (two) {
+        ld8(kp + key_off(j + NG), k1);
+        ld8(vp + key_off(j + NG), v1);
+      }
+      one_key(j, k0, v0);
+      if (two) one_key(j + NG, k1, v1);
+    }
+    MT am[GP], al[GP], aa[GP][8];
+#pragma unroll
+    for (int e = 0; e < GP; ++e) {
+      am[e] = (MT)m[e];
+      al[e] = (MT)l[e];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) aa[e][i] = (MT)acc[e][i];
+    }
+#pragma unroll
+    for (int o = LPR; o < 64; o <<= 1) {
+#pragma unroll
+      for (int e = 0; e < GP; ++e) {
+        if (ne[e]) {
+          const MT mo = __shfl_xor(am[e], o, 64), lo = __shfl_xor(al[e], o, 64);
+          const MT M = am[e] > mo ? am[e] : mo;
+          const MT wa = am[e] == NEG_INF ? (MT)0 : merge_exp(am[e] - M), wb = mo == NEG_INF ? (MT)0 : merge_exp(mo - M);
+          al[e] = al[e] * wa + lo * wb;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) aa[e][i] = aa[e][i] * wa + __shfl_xor(aa[e][i], o, 64) * wb;
+          am[e] = M;
+        }
+      }
+    }
+    const int wave = tid >> 6, lane = tid & 63;
+    if (lane < LPR) {
+#pragma unroll
+      for (int e = 0; e < GP; ++e) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) red[wave][e][sub * 8 + i] = aa[e][i];
+        if (sub == 0) { red[wave][e][LPR * 8] = am[e]; red[wave][e][LPR * 8 + 1] = al[e]; }
+      }
+    }
+    __syncthreads();
+    if (tid < GP * LPR) {
+      const int e = tid / LPR, pl = e >> gsh, g = e & gmask;   // (sub = tid % LPR as above)
+      if (g < G && p0 + pl < n_pos) {
+        MT M = NEG_INF;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) M = red[w][e][LPR * 8] > M ? red[w][e][LPR * 8] : M;
+        MT L = 0, o8[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o8[i] = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          const MT mw = red[w][e][LPR * 8];
+          const MT ww = mw == NEG_INF ? (MT)0 : merge_exp(mw - M);
+          L += red[w][e][LPR * 8 + 1] * ww;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) o8[i] += red[w][e][sub * 8 + i] * ww;
+        }
+        float of[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) of[i] = (float)(o8[i] / L);
+        st8(out + (q0 + p0 + pl) * ldo + (long)(kvh * G + g) * DH + sub * 8, of);
+      }
+    }
+    __syncthreads();   // the next pass writes `red` again
+  }
+}
+
+// One thread per candidate token t: src[2 t] = row, src[2 t + 1] = tok. tok >= 0: a candidate's FIRST token, read from the prefill's logits row of its prompt,
+// logits[row, tok] - lse[row] (phase 0, before the extend pass overwrites logits and stats); tok < 0: a later token, logit[target] - lse of extend row `row` as
+// logit_rows left them in stats (phase 1).
+__global__ __launch_bounds__(256) void cand_logp_kernel(const float* __restrict__ logits, long ld, int V, const float* __restrict__ stats, int n_rows,
+                                                        const int* __restrict__ src, int n, int phase, float* __restrict__ out) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n) return;
+  const int row = src[2 * t], tok = src[2 * t + 1];
+  if (row < 0 || row >= n_rows || tok >= V) return;   // (plan_candidates keeps both in range: never taken)
+  if (phase == 0) {
+    if (tok >= 0) out[t] = logits[(long)row * ld + tok] - stats[(long)row * 4];
+  } else if (tok < 0) out[t] = stats[(long)row * 4 + 1] - stats[(long)row * 4];
+}
+
 }  // namespace
 
 template <typename AT>
@@ -364,6 +515,31 @@ int attn_decode_shared(hipStream_t st, const AT* q, long ldq, const AT* kcache, 
   return CHECK_LAUNCH();
 }
 
+template <typename AT>
+int attn_extend(hipStream_t st, const AT* q, long ldq, const AT* kcache, const AT* vcache, const int* geo, int n_cands, int n_rows, AT* out, long ldo, int H, int Hkv,
+                int dh, float scale, long cap_rows) {
+  if (n_cands <= 0) return TST_OK;
+  if (!q || !kcache || !vcache || !geo || !out || Hkv < 1 || H < Hkv || H % Hkv || H / Hkv > 8 || (dh != 64 && dh != 128) || (ldq & 7) || (ldo & 7) ||
+      ldq < (long)H * dh || ldo < (long)H * dh || n_rows < 1 || cap_rows <= 0 || Hkv > 65535)
+    return TST_EINVAL;
+  const int G = H / Hkv;
+  const int gsh = G == 1 ? 0 : G == 2 ? 1 : G <= 4 ? 2 : 3;
+  const dim3 grid((unsigned)n_cands, (unsigned)Hkv);
+#define AE_LAUNCH(DH) \
+  hipLaunchKernelGGL((attn_extend_kernel<AT, DH, 8>), grid, dim3(256), 0, st, q, ldq, kcache, vcache, geo, n_rows, out, ldo, G, gsh, Hkv, scale, cap_rows)
+  if (dh == 128) AE_LAUNCH(128);
+  else AE_LAUNCH(64);
+#undef AE_LAUNCH
+  return CHECK_LAUNCH();
+}
+
+int cand_logp(hipStream_t st, const float* logits, long ld, int V, const float* stats, int n_rows, const int* src, int n, int phase, float* out) {
+  if (n <= 0) return TST_OK;
+  if (!logits || !stats || !src || !out || V < 1 || ld < V || n_rows < 1 || (phase != 0 && phase != 1)) return TST_EINVAL;
+  hipLaunchKernelGGL(cand_logp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, logits, ld, V, stats, n_rows, src, n, phase, out);
+  return CHECK_LAUNCH();
+}
+
 int next_token(hipStream_t st, const float* stats, const int* meta, int n_seqs, int j, int* tok, float* logp, int* d_ids, int* d_pos, int* lab_idx) {
   if (n_seqs <= 0) return TST_OK;
   if (!stats || !meta || !tok || !logp || !d_ids || !d_pos || !lab_idx || j < 0) return TST_EINVAL;
@@ -385,6 +561,7 @@ int sample_rows(hipStream_t st, const float* logits, long ld, int V, const int* 
   template int attn_decode<AT>(hipStream_t, const AT*, long, const AT*, const AT*, const int*, int, int, AT*, long, int, int, int, \
                                float, long);                                                                                        \
   template int attn_decode_shared<AT>(hipStream_t, const AT*, long, const AT*, const AT*, const int*, int, int, AT*, long, int, int, \
-                                      int, float, long);
+                                      int, float, long);                                                                             \
+  template int attn_extend<AT>(hipStream_t, const AT*, long, const AT*, const AT*, const int*, int, int, AT*, long, int, int, int, float, long);
 INSTANTIATE(bf16_t)
 INSTANTIATE(float)

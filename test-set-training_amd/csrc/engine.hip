@@ -298,6 +298,14 @@ struct tst_ctx {
   int gen_samples = 0;          // 0: the pending generation is greedy; n >= 1: sampled with n draws per prompt
   int *smp_seeds = nullptr, *h_smp_seeds = nullptr;   // sampled generations: low | high word of every sequence's seed [2 Smax] and its pinned staging image (first tst_sample_async)
   std::vector<int> gen_eos;
+  // Candidate scoring (tst_score_candidates_async; kernels in decode.hip, row map in host_logic.h plan_candidates): the generation's cache and pending slot, and a
+  // block of its own allocated by the first such call of the context: cand_dev = geo | ext_rows | src (cand_dev_ints) | logp_tok [Rmax]; h_cand = the pinned
+  // staging image of the first three, then ids | pos | lab_idx | targets of the extend rows [4 x cand_ext_cap] and logp_tok [Rmax] of the pending call.
+  int* cand_dev = nullptr;
+  int* h_cand = nullptr;
+  int cand_n_ext = 0;           // candidates with at least two tokens of the call being enqueued: attn_extend's workgroups per kv head
+  int gen_cand = 0;             // n >= 1: the pending generation is a tst_score_candidates_async over n candidates (gen_S counts their tokens)
+  std::vector<int> cand_cu;
   // Token attribution (tst_attribute_async; kernels in attribute.hip, row weights and the fetch side in host_logic.h). Allocated by the first attribution of the
   // context. attr_dev = row weights [Rmax] | row kinds [Rmax] | option ids [256] | gxi [Tmax] | gnorm [Tmax] (4-byte words); h_attr = the pinned staging image of the
   // first three, then gxi | gnorm | row statistics [Rmax * 4] of the pending attribution. forward() and backward() take the pass of an attribution as their AttrPass
@@ -1043,6 +1051,8 @@ int tail_fwd(CtxT<AT>* ctx, LayerT<AT>& W, const Rows& rows, const TailBufsT<AT>
 // what a generation asks of forward(): mode 0 = the graph every other entry point runs; 1 = the prefill (RoPE as its own pass, k | v of every layer appended to
 // the cache); 2 = decode step `step` (one row per sequence, positions from d_pos, attn_decode against the cache). shared: a sampled generation -- gen_dev
 // holds plan_sample's image, a decode row attends to its prompt's shared rows and its own tail (attn_decode_shared)
+// mode 3 = the extend pass of a candidate scoring: a decode step over the rows "candidate c, position p", k | v rows and geometry from cand_dev, all positions
+// of a candidate in one attention launch (attn_extend)
 struct GenPass {
   int mode = 0, step = 0;
   bool shared = false;
@@ -1106,7 +1116,8 @@ int forward(CtxT<AT>* ctx, bool stash, GenPass gen = {}, AttrPass ap = {}) {
       AT* vc = kc + ctx->gen_rows * wkv;
       const int S = ctx->cur_S;
       const long o_pre = gen.shared ? (long)tsthost::sample_off_prefill(batch_limits(ctx)) : 3 + 2 * ctx->Smax;
-      const int* krows = ctx->gen_dev + o_pre + (gen.mode == 1 ? 0L : ctx->Tmax + (long)(gen.step - 1) * S);
+      const int* krows = gen.mode == 3 ? ctx->cand_dev + (long)tsthost::cand_off_rows(batch_limits(ctx))
+                                       : ctx->gen_dev + o_pre + (gen.mode == 1 ? 0L : ctx->Tmax + (long)(gen.step - 1) * S);
       CTX_RC(kv_append<AT>(st, A.qkv, ctx->dqkv, ctx->dq, krows, kc, vc, T, ctx->Hkv, ctx->dh, ctx->gen_rows));
       if (gen.mode == 2) {
         const int slot = prof_begin(ctx, st, ctx->prof_hbm);
@@ -1115,9 +1126,13 @@ int forward(CtxT<AT>* ctx, bool stash, GenPass gen = {}, AttrPass ap = {}) {
         else
         CTX_RC(attn_decode<AT>(st, A.qkv, ctx->dqkv, kc, vc, ctx->gen_dev, S, gen.step, A.attn, ctx->dattn, ctx->H, ctx->Hkv, ctx->dh, scale, ctx->gen_rows));
         prof_end(ctx, st, slot, PROF_ATTN, 1, 4.0 * ctx->cur_sumsq_len * ctx->H * ctx->dh);   // q . K^T + P . V over the cached keys (cur_sumsq_len = their count)
+      } else if (gen.mode == 3) {
+        const int slot = prof_begin(ctx, st, ctx->prof_hbm);
+        CTX_RC(attn_extend<AT>(st, A.qkv, ctx->dqkv, kc, vc, ctx->cand_dev, ctx->cand_n_ext, T, A.attn, ctx->dattn, ctx->H, ctx->Hkv, ctx->dh, scale, ctx->gen_rows));
+        prof_end(ctx, st, slot, PROF_ATTN, 1, 4.0 * ctx->cur_sumsq_len * ctx->H * ctx->dh);
       }
     }
-    if (gen.mode != 2) {
+    if (gen.mode < 2) {
       const int slot = prof_begin(ctx, st, ctx->prof_hbm);
       if (whatif() & 2) {
       } else if constexpr (sizeof(AT) == 2)
@@ -2587,6 +2602,7 @@ int generate_async_impl(CtxT<AT>* ctx, const tst_batch* b, int32_t max_new, cons
   ctx->gen_S = S;
   ctx->gen_new = max_new;
   ctx->gen_samples = 0;
+  ctx->gen_cand = 0;
   return TST_OK;
 }
 
@@ -2665,6 +2681,97 @@ int sample_async_impl(CtxT<AT>* ctx, const tst_batch* b, int32_t max_new, int32_
   ctx->gen_S = R;
   ctx->gen_new = max_new;
   ctx->gen_samples = n_samples;
+  ctx->gen_cand = 0;
+  return TST_OK;
+}
+
+// ---- candidate scoring: ONE prefill over the S prompts, then ONE forward pass over the R_e extend rows "candidate c, position p" (include/tst_hip.h
+// tst_score_candidates_async; kernels in decode.hip, row map in host_logic.h plan_candidates). The cache and the pending slot are the generation's (a one-token
+// generation's cache holds T + R_e rows); the geometry image and the output block are the call's own.
+int cand_reserve(tst_ctx* ctx) {
+  const tsthost::BatchLimits lim = batch_limits(ctx);
+  const size_t ints = tsthost::cand_dev_ints(lim);
+  if (!ctx->cand_dev) {
+    ctx->cand_dev = (int*)ctx->pool.alloc((int64_t)(ints + (size_t)ctx->Rmax) * 4);
+    if (!ctx->cand_dev) return fail(ctx, TST_ENOMEM, "hipMalloc failed: buffers of the candidate scoring");
+    CTX_HIP(hipStreamSynchronize(nullptr));   // (the pool's zero fill, as in gen_reserve)
+  }
+  if (!ctx->h_cand) CTX_HIP(hipHostMalloc((void**)&ctx->h_cand, (ints + 4 * (size_t)tsthost::cand_ext_cap(lim) + (size_t)ctx->Rmax) * 4, hipHostMallocDefault));
+  return TST_OK;
+}
+
+template <typename AT>
+int score_candidates_async_impl(CtxT<AT>* ctx, const tst_batch* b, const int32_t* cand_ids, const int32_t* cu_cand, const int32_t* cand_seq, int32_t n_cands) {
+  if (!b) return TST_EINVAL;
+  if (!ctx->finalized) return fail(ctx, TST_ESTATE, "weights not finalised");
+  ctx->err.clear();
+  const tsthost::BatchLimits lim = batch_limits(ctx);
+  tsthost::CandPlan plan;
+  {
+    std::string perr;
+    if (tsthost::plan_candidates(b, lim, cand_ids, cu_cand, cand_seq, n_cands, plan, perr) != TST_OK) return fail(ctx, TST_EINVAL, perr);
+  }
+  if (ctx->H % ctx->Hkv || ctx->H / ctx->Hkv > 8 || (ctx->dh != 64 && ctx->dh != 128))
+    return fail(ctx, TST_EINVAL, "generation needs head_dim 64 or 128 and at most 8 query heads per kv head");
+  hipStream_t st = ctx->stream;
+  const int S = plan.S, R = plan.R_e, N = plan.n_tok;
+  CTX_RC(upload_batch(ctx, b, false, plan.last_rows.data(), S));   // (refuses a host id outside the vocabulary before anything is allocated or grown)
+  ctx->gen_S = -1;
+  CTX_RC(gen_reserve(ctx, 1));
+  CTX_RC(cand_reserve(ctx));
+  CTX_RC(ctx_event_sync(ctx, ctx->gen_evt));   // the staging images may still feed the previous call's copies
+  const size_t o_pre = tsthost::sample_off_prefill(lim), o_rows = tsthost::cand_off_rows(lim), o_src = tsthost::cand_off_src(lim), ints = tsthost::cand_dev_ints(lim);
+  const size_t cap_e = (size_t)tsthost::cand_ext_cap(lim);
+  int* h = ctx->h_cand;
+  int* h_ext = h + ints;                               // ids | pos | lab_idx | targets of the extend rows
+  float* h_out = (float*)(h_ext + 4 * cap_e);
+  float* d_out = (float*)(ctx->cand_dev + ints);
+  {
+    memcpy(ctx->h_gen + o_pre, plan.prefill_rows.data(), plan.prefill_rows.size() * sizeof(int));
+    CTX_HIP(hipMemcpyAsync(ctx->gen_dev + o_pre, ctx->h_gen + o_pre, plan.prefill_rows.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    if (!plan.geo.empty()) memcpy(h, plan.geo.data(), plan.geo.size() * sizeof(int));
+    if (R > 0) memcpy(h + o_rows, plan.ext_rows.data(), (size_t)R * sizeof(int));
+    memcpy(h + o_src, plan.src.data(), plan.src.size() * sizeof(int));
+    CTX_HIP(hipMemcpyAsync(ctx->cand_dev, h, (o_src + plan.src.size()) * sizeof(int), hipMemcpyHostToDevice, st));
+    for (int r = 0; r < R; ++r) {
+      h_ext[r] = plan.ext_ids[(size_t)r];
+      h_ext[cap_e + r] = plan.ext_pos[(size_t)r];
+      h_ext[2 * cap_e + r] = r;   // the head reads every row of the extend pass
+      h_ext[3 * cap_e + r] = plan.ext_tgt[(size_t)r];
+    }
+  }
+  const int* d_src = ctx->cand_dev + o_src;
+  CTX_RC(forward(ctx, false, GenPass{1, 0, true}));   // prefill: the sampled generation's, prompts at cache rows 0 .. T
+  CTX_RC(head_forward(ctx, false));
+  CTX_RC(logit_rows<AT>(st, ctx->logits, ctx->Vp, ctx->d_targets, S, ctx->V, ctx->stats, nullptr, 0, 0.f, nullptr, 0, ctx->optl));   // (for its lse)
+  // first tokens: from prompt s's one logits row, before the extend pass overwrites logits and stats
+  CTX_RC(cand_logp(st, ctx->logits, ctx->Vp, ctx->V, ctx->stats, S, d_src, N, 0, d_out));
+  if (R > 0) {
+    // the extend pass: forward() over one row per (candidate, position); ids, positions, head rows and targets were laid out on the host
+    const size_t rb = (size_t)R * sizeof(int);
+    CTX_HIP(hipMemcpyAsync(ctx->d_ids, h_ext, rb, hipMemcpyHostToDevice, st));
+    CTX_HIP(hipMemcpyAsync(ctx->d_pos, h_ext + cap_e, rb, hipMemcpyHostToDevice, st));
+    CTX_HIP(hipMemcpyAsync(ctx->d_lab_idx, h_ext + 2 * cap_e, rb, hipMemcpyHostToDevice, st));
+    CTX_HIP(hipMemcpyAsync(ctx->d_targets, h_ext + 3 * cap_e, rb, hipMemcpyHostToDevice, st));
+    ctx->cur_T = ctx->cur_S = ctx->cur_R = R;
+    ctx->cur_maxlen = 1;
+    ctx->cand_n_ext = plan.n_ext;
+    for (int q = 0; q < TST_MAX_STACK; ++q) ctx->slot_ends.t_end[q] = ctx->row_ends.t_end[q] = plan.slot_r_end[q];
+    double keys = 0;
+    for (int r = 0; r < R; ++r) keys += (double)plan.ext_pos[(size_t)r] + 1.0;
+    ctx->cur_sumsq_len = keys;
+    CTX_RC(forward(ctx, false, GenPass{3, 0, true}));
+    CTX_RC(head_forward(ctx, false));
+    CTX_RC(logit_rows<AT>(st, ctx->logits, ctx->Vp, ctx->d_targets, R, ctx->V, ctx->stats, nullptr, 0, 0.f, nullptr, 0, ctx->optl));
+    CTX_RC(cand_logp(st, ctx->logits, ctx->Vp, ctx->V, ctx->stats, R, d_src, N, 1, d_out));
+  }
+  CTX_HIP(hipMemcpyAsync(h_out, d_out, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+  CTX_HIP(hipEventRecord(ctx->gen_evt, st));
+  ctx->cand_cu.assign(cu_cand, cu_cand + n_cands + 1);
+  ctx->gen_S = N;
+  ctx->gen_new = 0;
+  ctx->gen_samples = 0;
+  ctx->gen_cand = n_cands;
   return TST_OK;
 }
 
@@ -2961,6 +3068,7 @@ int tst_destroy(tst_ctx* ctx) {
   if (ctx->h_gen) (void)hipHostFree(ctx->h_gen);
   if (ctx->h_attr) (void)hipHostFree(ctx->h_attr);
   if (ctx->h_smp_seeds) (void)hipHostFree(ctx->h_smp_seeds);
+  if (ctx->h_cand) (void)hipHostFree(ctx->h_cand);
   if (ctx->h_ig) (void)hipHostFree(ctx->h_ig);
   if (ctx->attr_evt) (void)hipEventDestroy(ctx->attr_evt);
   if (ctx->gen_evt) (void)hipEventDestroy(ctx->gen_evt);
@@ -3411,6 +3519,7 @@ static int gen_fetch_rows(tst_ctx* ctx, const char* what, int32_t* tokens_out, f
 
 int tst_generate_fetch(tst_ctx* ctx, int32_t* tokens_out, float* logp_out, int32_t* n_new_out) {
   if (!ctx) return TST_EINVAL;
+  if (ctx->gen_S >= 0 && ctx->gen_cand > 0) return fail(ctx, TST_ESTATE, "the pending call is a tst_score_candidates_async: fetch it with tst_score_candidates_fetch");
   if (ctx->gen_S >= 0 && ctx->gen_samples > 0) return fail(ctx, TST_ESTATE, "the pending generation is a tst_sample_async: fetch it with tst_sample_fetch");
   return gen_fetch_rows(ctx, "tst_generate_fetch without a pending tst_generate_async", tokens_out, logp_out, n_new_out);
 }
@@ -3423,6 +3532,7 @@ int tst_sample_async(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, i
 
 int tst_sample_fetch(tst_ctx* ctx, int32_t* tokens_out, float* logp_out, int32_t* n_new_out) {
   if (!ctx) return TST_EINVAL;
+  if (ctx->gen_S >= 0 && ctx->gen_cand > 0) return fail(ctx, TST_ESTATE, "the pending call is a tst_score_candidates_async: fetch it with tst_score_candidates_fetch");
   if (ctx->gen_S >= 0 && ctx->gen_samples == 0) return fail(ctx, TST_ESTATE, "the pending generation is a tst_generate_async: fetch it with tst_generate_fetch");
   return gen_fetch_rows(ctx, "tst_sample_fetch without a pending tst_sample_async", tokens_out, logp_out, n_new_out);
 }
@@ -3432,6 +3542,38 @@ int tst_sample(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, int32_t
   int rc = tst_sample_async(ctx, b, max_new_tokens, n_samples, temperature, seq_seeds, eos_ids, n_eos);
   if (rc != TST_OK) return rc;
   return tst_sample_fetch(ctx, tokens_out, logp_out, n_new_out);
+}
+
+int tst_score_candidates_async(tst_ctx* ctx, const tst_batch* b, const int32_t* cand_ids, const int32_t* cu_cand, const int32_t* cand_seq, int32_t n_cands) {
+  if (!ctx || !b) return TST_EINVAL;
+  return typed(ctx, [&](auto* c) { return score_candidates_async_impl(c, b, cand_ids, cu_cand, cand_seq, n_cands); });
+}
+
+int tst_score_candidates_fetch(tst_ctx* ctx, float* logp_tok_out, float* logp_cand_out) {
+  if (!ctx) return TST_EINVAL;
+  if (ctx->gen_S >= 0 && ctx->gen_cand == 0)
+    return fail(ctx, TST_ESTATE, ctx->gen_samples > 0 ? "the pending generation is a tst_sample_async: fetch it with tst_sample_fetch"
+                                                      : "the pending generation is a tst_generate_async: fetch it with tst_generate_fetch");
+  int N;
+  CTX_RC(take_pending(ctx, ctx->gen_S, ctx->gen_evt, "tst_score_candidates_fetch without a pending tst_score_candidates_async", N));
+  const tsthost::BatchLimits lim = batch_limits(ctx);
+  const float* h_out = (const float*)(ctx->h_cand + tsthost::cand_dev_ints(lim) + 4 * (size_t)tsthost::cand_ext_cap(lim));
+  if (logp_tok_out) memcpy(logp_tok_out, h_out, (size_t)N * 4);
+  if (logp_cand_out)
+    for (int c = 0; c < ctx->gen_cand; ++c) {
+      double acc = 0.0;   // in token order, rounded once
+      for (int t = ctx->cand_cu[(size_t)c]; t < ctx->cand_cu[(size_t)c + 1]; ++t) acc += (double)h_out[t];
+      logp_cand_out[c] = (float)acc;
+    }
+  ctx->gen_cand = 0;
+  return TST_OK;
+}
+
+int tst_score_candidates(tst_ctx* ctx, const tst_batch* b, const int32_t* cand_ids, const int32_t* cu_cand, const int32_t* cand_seq, int32_t n_cands,
+                         float* logp_tok_out, float* logp_cand_out) {
+  int rc = tst_score_candidates_async(ctx, b, cand_ids, cu_cand, cand_seq, n_cands);
+  if (rc != TST_OK) return rc;
+  return tst_score_candidates_fetch(ctx, logp_tok_out, logp_cand_out);
 }
 
 int tst_generate(tst_ctx* ctx, const tst_batch* b, int32_t max_new_tokens, const int32_t* eos_ids, int32_t n_eos, int32_t* tokens_out, float* logp_out,

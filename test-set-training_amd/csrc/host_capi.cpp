@@ -133,6 +133,32 @@ int tst_host_plan_sample(const tst_model_cfg* cfg, const tst_batch* b, int max_n
   return TST_OK;
 }
 
+int tst_host_plan_candidates(const tst_model_cfg* cfg, const tst_batch* b, const int32_t* cand_ids, const int32_t* cu_cand, const int32_t* cand_seq, int n_cands,
+                             int64_t* out_ints, int32_t* geo_out, int32_t* ext_rows_out, int32_t* ext_ids_out, int32_t* ext_pos_out, int32_t* ext_tgt_out,
+                             int32_t* src_out, int32_t* last_rows_out, char* err_out, int err_cap) {
+  if (!cfg || !out_ints) return TST_EINVAL;
+  tsthost::CandPlan g;
+  std::string err;
+  const tsthost::BatchLimits lim = limits_of(*cfg);
+  const int rc = tsthost::plan_candidates(b, lim, cand_ids, cu_cand, cand_seq, n_cands, g, err);
+  if (err_out && err_cap > 0) {
+    strncpy(err_out, err.c_str(), (size_t)err_cap - 1);
+    err_out[err_cap - 1] = 0;
+  }
+  if (rc != TST_OK) return rc;
+  int64_t* o = out_ints;
+  *o++ = g.S; *o++ = g.T; *o++ = g.n_tok; *o++ = g.R_e; *o++ = g.n_ext; *o++ = g.rows_used; *o++ = tsthost::gen_cache_rows(lim, 1);
+  *o++ = (int64_t)tsthost::cand_dev_ints(lim);
+  for (int q = 0; q < tsthost::kMaxStack; ++q) *o++ = g.slot_r_end[q];
+  auto put = [](int32_t* dst, const std::vector<int>& v) {
+    if (dst)
+      for (size_t i = 0; i < v.size(); ++i) dst[i] = v[i];
+  };
+  put(geo_out, g.geo); put(ext_rows_out, g.ext_rows); put(ext_ids_out, g.ext_ids); put(ext_pos_out, g.ext_pos); put(ext_tgt_out, g.ext_tgt);
+  put(src_out, g.src); put(last_rows_out, g.last_rows);
+  return TST_OK;
+}
+
 int tst_host_cut_at_eos(int32_t* tokens, float* logp, int32_t* n_new_out, int n_seqs, int max_new, const int32_t* eos_ids, int n_eos) {
   if (!tokens || n_seqs < 0 || max_new < 1 || n_eos < 0 || (n_eos > 0 && !eos_ids)) return TST_EINVAL;
   tsthost::cut_at_eos(tokens, logp, n_new_out, n_seqs, max_new, eos_ids, n_eos);

@@ -8,6 +8,7 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 #include <utility>
 #include <vector>
@@ -432,6 +433,118 @@ inline int plan_sample(const tst_batch* b, const BatchLimits& lim, int max_new, 
   }
   for (int q = 0; q < kMaxStack; ++q) out.slot_r_end[q] = g.slot_s_end[q] * n_samples;
   out.rows_used = (long)T + R * max_new;
+  return TST_OK;
+}
+// ------------------------------------------------------------------------------------------------ candidate scoring: validation + the extend row map
+// tst_score_candidates_async scores n_cands given continuations of the packed prompts at ONE prefill: candidate c = tokens [cu_cand[c], cu_cand[c + 1]) continues
+// prompt cand_seq[c]. Its first token is read from the prompt's one logits row; every later token c_{p + 1} needs the model's output behind c_p, so candidate c
+// adds L_c - 1 "extend rows" (c, p), p = 0 .. L_c - 2, ordered c-major (cand_seq is non-decreasing: the rows keep the prompts' slot order). Row (c, p) is fed c_p at
+// position len + p and its k | v go to cache row T + (cu_cand[c] - c) + p: the tails packed behind the prompts at rows 0 .. T, a one-token candidate taking none.
+// That fits the cache of a one-token generation (gen_cache_rows(l, 1) = max_tokens + max_seqs) because R_e <= max_seqs. plan_candidates refuses what the engine
+// cannot run BEFORE anything is allocated or launched and fills the images:
+//   geo          [5 n_ext]   {pre_row0, len, tail_row0, q_row0, n_pos} per candidate with L_c >= 2, in candidate order   (what attn_extend reads)
+//   ext_rows     [R_e]       cache row of every extend row (what kv_append reads)
+//   src          [2 n_tok]   {row, tok} per candidate token, what cand_logp reads: first tokens {prompt s, c_0}, later ones {extend row of (c, p - 1), -1}
+//   ext_ids / ext_pos / ext_tgt [R_e]   input id, position and head target c_{p + 1} of every extend row
+//   last_rows    [S]         packed index of every prompt's last token;   prefill_rows [T] = 0 .. T - 1
+//   slot_r_end   [kMaxStack] extend rows of the prompts in slots 0 .. q
+// b->input_ids is never dereferenced (it may be a device pointer); the candidates' ids are host memory.
+constexpr int kCandMaxLen = 16;   // == TST_CAND_MAX_LEN
+inline int cand_ext_cap(const BatchLimits& l) { return std::min(l.Tmax, std::min(l.Smax, l.Rmax)); }
+inline size_t cand_off_rows(const BatchLimits& l) { return 5 * (size_t)cand_ext_cap(l); }
+inline size_t cand_off_src(const BatchLimits& l) { return 6 * (size_t)cand_ext_cap(l); }
+// ints of the call's own device image at capacity: geo | ext_rows | src
+inline size_t cand_dev_ints(const BatchLimits& l) { return cand_off_src(l) + 2 * (size_t)l.Rmax; }
+struct CandPlan {
+  int S = 0, T = 0, n_cands = 0, n_tok = 0, R_e = 0, n_ext = 0;
+  long rows_used = 0;   // rows of the cache this call touches: T + R_e (<= gen_cache_rows(l, 1))
+  std::vector<int> geo, ext_rows, src, ext_ids, ext_pos, ext_tgt, last_rows, prefill_rows;
+  int slot_r_end[kMaxStack];
+};
+inline int plan_candidates(const tst_batch* b, const BatchLimits& lim, const int32_t* cand_ids, const int32_t* cu_cand, const int32_t* cand_seq, int n_cands,
+                           CandPlan& out, std::string& err) {
+  auto fail = [&](const char* m) { err = m; return TST_EINVAL; };
+  if (!b) return fail("null batch");
+  const int T = b->n_tokens, S = b->n_seqs;
+  if (T <= 0 || S <= 0 || T > lim.Tmax || S > lim.Smax) return fail("batch exceeds max_tokens/max_seqs or is empty");
+  if (S > lim.Rmax) return fail("more sequences than max_labelled: the head runs on one row per sequence");
+  if (!b->input_ids || !b->cu_seqlens) return fail("null batch pointers");
+  if (b->cu_seqlens[0] != 0 || b->cu_seqlens[S] != T) return fail("cu_seqlens must start at 0 and end at n_tokens");
+  if (n_cands < 1) return fail("n_cands must be at least 1");
+  if (!cand_ids || !cu_cand || !cand_seq) return fail("null candidate pointers");
+  out = CandPlan();
+  out.S = S; out.T = T; out.n_cands = n_cands;
+  out.last_rows.assign((size_t)S, 0);
+  out.prefill_rows.assign((size_t)T, 0);
+  for (int t = 0; t < T; ++t) out.prefill_rows[(size_t)t] = t;
+  std::vector<int> slot_of((size_t)S, 0);
+  int cur_slot = 0;
+  for (int s = 0; s < S; ++s) {
+    const int s0 = b->cu_seqlens[s], s1 = b->cu_seqlens[s + 1];
+    if (s0 < 0 || s1 > T || s1 < s0) return fail("cu_seqlens must be non-decreasing and within n_tokens");
+    const int len = s1 - s0;
+    if (len <= 0 || len > lim.max_position) return fail("sequence length out of range (1..max_position)");
+    if (b->seq_slot) {
+      const int sl = b->seq_slot[s];
+      if (sl < cur_slot || sl >= lim.ns) return fail("seq_slot must be non-decreasing and < n_stack");
+      cur_slot = sl;
+      slot_of[(size_t)s] = sl;
+    }
+    out.last_rows[(size_t)s] = s1 - 1;
+  }
+  if (cu_cand[0] != 0) return fail("cu_cand must start at 0 and increase strictly");
+  const long ext_cap = cand_ext_cap(lim);
+  long n_tok = 0, R_e = 0;
+  int prev_seq = 0;
+  for (int c = 0; c < n_cands; ++c) {
+    const long L = (long)cu_cand[c + 1] - (long)cu_cand[c];
+    if (L < 1) return fail("cu_cand must start at 0 and increase strictly");
+    if (L > kCandMaxLen) return fail("a candidate is longer than TST_CAND_MAX_LEN (16) tokens");
+    n_tok += L;
+    if (n_tok > lim.Rmax) return fail("the candidates' tokens exceed max_labelled");
+    const int s = cand_seq[c];
+    if (s < 0 || s >= S) return fail("cand_seq out of range (0..n_seqs-1)");
+    if (s < prev_seq) return fail("cand_seq must be non-decreasing");
+    prev_seq = s;
+    const int len = b->cu_seqlens[s + 1] - b->cu_seqlens[s];
+    if ((long)len + L - 1 > lim.max_position) return fail("prompt length + candidate length - 1 exceeds max_position");
+    for (long p = 0; p < L; ++p) {
+      const int id = cand_ids[cu_cand[c] + p];
+      if (id < 0 || id >= lim.V) return fail("candidate id out of vocabulary");
+    }
+    R_e += L - 1;
+    if (R_e > ext_cap) return fail("the candidates' extend rows (sum of length - 1) exceed min(max_tokens, max_seqs, max_labelled)");
+  }
+  out.n_tok = (int)n_tok; out.R_e = (int)R_e;
+  out.src.assign(2 * (size_t)n_tok, 0);
+  out.ext_rows.assign((size_t)R_e, 0);
+  out.ext_ids.assign((size_t)R_e, 0);
+  out.ext_pos.assign((size_t)R_e, 0);
+  out.ext_tgt.assign((size_t)R_e, 0);
+  for (int q = 0; q < kMaxStack; ++q) out.slot_r_end[q] = 0;
+  int r = 0;
+  for (int c = 0; c < n_cands; ++c) {
+    const int c0 = cu_cand[c], L = cu_cand[c + 1] - c0, s = cand_seq[c];
+    const int s0 = b->cu_seqlens[s], len = b->cu_seqlens[s + 1] - s0;
+    const int tail0 = T + (c0 - c);
+    out.src[2 * (size_t)c0] = s;
+    out.src[2 * (size_t)c0 + 1] = cand_ids[c0];
+    if (L >= 2) {
+      const int g[5] = {s0, len, tail0, r, L - 1};
+      out.geo.insert(out.geo.end(), g, g + 5);
+      ++out.n_ext;
+    }
+    for (int p = 0; p + 1 < L; ++p, ++r) {
+      out.ext_rows[(size_t)r] = tail0 + p;
+      out.ext_ids[(size_t)r] = cand_ids[c0 + p];
+      out.ext_pos[(size_t)r] = len + p;
+      out.ext_tgt[(size_t)r] = cand_ids[c0 + p + 1];
+      out.src[2 * (size_t)(c0 + p + 1)] = r;
+      out.src[2 * (size_t)(c0 + p + 1) + 1] = -1;
+    }
+    for (int q = slot_of[(size_t)s]; q < kMaxStack; ++q) out.slot_r_end[q] = r;
+  }
+  out.rows_used = (long)T + R_e;
   return TST_OK;
 }
 // the fetch side: row s of tokens / logp [S, max_new] is cut behind its first token that is in eos_ids -- n_new[s] counts that token, the entries behind

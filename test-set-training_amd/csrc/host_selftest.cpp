@@ -349,6 +349,125 @@ static void test_plan_sample() {
   }
 }
 
+// plan_candidates: prompts at rows 0 .. T, the candidates' tails packed behind them in c-major order -- the row map injective and inside the cache, a one-token
+// candidate taking no row; ids / positions / targets of every extend row; the {row, tok} source of every candidate token; slot boundaries; every refusal with its
+// message. Random ragged prompt batches and candidate lists, arrays at their exact sizes.
+static void test_plan_candidates() {
+  std::mt19937 rng(53u);
+  for (int it = 0; it < 300; ++it) {
+    const int ns = (it % 3 == 0) ? 1 + (int)(rng() % 4u) : 1;
+    const int S = ns + (int)(rng() % 6u), max_len = 1 + (int)(rng() % 40u), V = 50;
+    Batch x = make_batch(rng, S, max_len, V, ns, false);
+    x.b.input_ids = (const int32_t*)(uintptr_t)16;   // never dereferenced
+    const int T = x.b.n_tokens;
+    // 0 .. 4 candidates per prompt (at least one over all), lengths 1 .. 16 with every third one a single token
+    std::vector<int32_t> cseq, ccu(1, 0), cids;
+    for (int s = 0; s < S; ++s) {
+      const int nc = (int)(rng() % 5u) + (s == S - 1 && cseq.empty() ? 1 : 0);
+      for (int i = 0; i < nc; ++i) {
+        const int L = (rng() % 3u == 0) ? 1 : 1 + (int)(rng() % (unsigned)kCandMaxLen);
+        for (int p = 0; p < L; ++p) cids.push_back((int32_t)(rng() % (unsigned)V));
+        ccu.push_back((int32_t)cids.size());
+        cseq.push_back(s);
+      }
+    }
+    const int NC = (int)cseq.size(), N = (int)cids.size(), R = N - NC;
+    std::unique_ptr<int32_t[]> e_ids(new int32_t[(size_t)N]), e_cu(new int32_t[(size_t)NC + 1]), e_seq(new int32_t[(size_t)NC]);
+    std::copy(cids.begin(), cids.end(), e_ids.get());
+    std::copy(ccu.begin(), ccu.end(), e_cu.get());
+    std::copy(cseq.begin(), cseq.end(), e_seq.get());
+    const int big = std::max(std::max(T, S), std::max(R, 1));
+    const BatchLimits lim = {big + (int)(rng() % 3u), big + (int)(rng() % 3u), std::max(N, S), V, max_len + kCandMaxLen - 1, ns};
+    CandPlan g;
+    std::string err;
+    CHECK(plan_candidates(&x.b, lim, e_ids.get(), e_cu.get(), e_seq.get(), NC, g, err) == TST_OK);
+    const long cap = gen_cache_rows(lim, 1);
+    CHECK(g.S == S && g.T == T && g.n_cands == NC && g.n_tok == N && g.R_e == R && g.rows_used == (long)T + R && g.rows_used <= cap);
+    CHECK((int)g.ext_rows.size() == R && (int)g.ext_ids.size() == R && (int)g.ext_pos.size() == R && (int)g.ext_tgt.size() == R && (int)g.src.size() == 2 * N);
+    CHECK((int)g.geo.size() == 5 * g.n_ext && (int)g.last_rows.size() == S && (int)g.prefill_rows.size() == T);
+    // the image fits what the context allocates, every part at its offset
+    CHECK(g.geo.size() <= cand_off_rows(lim) && cand_off_rows(lim) + g.ext_rows.size() <= cand_off_src(lim) && cand_off_src(lim) + g.src.size() <= cand_dev_ints(lim));
+    std::vector<char> seen((size_t)cap, 0);
+    for (int t = 0; t < T; ++t) {
+      CHECK(g.prefill_rows[(size_t)t] == t);
+      seen[(size_t)t] = 1;
+    }
+    int r = 0, e = 0;
+    for (int c = 0; c < NC; ++c) {
+      const int c0 = ccu[(size_t)c], L = ccu[(size_t)c + 1] - c0, s = cseq[(size_t)c];
+      const int s0 = x.cu[(size_t)s], len = x.cu[(size_t)s + 1] - s0;
+      CHECK(g.src[2 * (size_t)c0] == s && g.src[2 * (size_t)c0 + 1] == cids[(size_t)c0]);
+      if (L >= 2) {
+        const int* q = g.geo.data() + 5 * (size_t)e++;
+        CHECK(q[0] == s0 && q[1] == len && q[2] == T + r && q[3] == r && q[4] == L - 1);   // tails packed in c-major order: the tail starts where the last one ended
+      }
+      for (int p = 0; p + 1 < L; ++p, ++r) {
+        const int row = g.ext_rows[(size_t)r];
+        CHECK(row == T + (c0 - c) + p && row == T + r && row >= T && row < cap);
+        if (row >= 0 && row < cap) { CHECK(!seen[(size_t)row]); seen[(size_t)row] = 1; }
+        CHECK(g.ext_ids[(size_t)r] == cids[(size_t)c0 + p] && g.ext_pos[(size_t)r] == len + p && g.ext_tgt[(size_t)r] == cids[(size_t)c0 + p + 1]);
+        CHECK(g.src[2 * (size_t)(c0 + p + 1)] == r && g.src[2 * (size_t)(c0 + p + 1) + 1] == -1);
+      }
+    }
+    CHECK(r == R && e == g.n_ext);
+    for (int s = 0; s < S; ++s) CHECK(g.last_rows[(size_t)s] == x.cu[(size_t)s + 1] - 1);
+    for (int q = 0; q < kMaxStack; ++q) {
+      int want = 0;
+      for (int c = 0; c < NC; ++c)
+        if ((ns > 1 ? x.slot[(size_t)cseq[(size_t)c]] : 0) <= q) want += ccu[(size_t)c + 1] - ccu[(size_t)c] - 1;
+      CHECK(g.slot_r_end[q] == want);
+    }
+    // refusals
+    CandPlan rr;
+    auto refused = [&](const BatchLimits& l, const int32_t* ids, const int32_t* cu, const int32_t* seq, int n, const char* what) {
+      err.clear();
+      return plan_candidates(&x.b, l, ids, cu, seq, n, rr, err) == TST_EINVAL && err.find(what) != std::string::npos;
+    };
+    CHECK(plan_candidates(nullptr, lim, e_ids.get(), e_cu.get(), e_seq.get(), NC, rr, err) == TST_EINVAL);
+    CHECK(refused(lim, e_ids.get(), e_cu.get(), e_seq.get(), 0, "n_cands"));
+    CHECK(refused(lim, nullptr, e_cu.get(), e_seq.get(), NC, "null candidate"));
+    { std::vector<int32_t> cu2(ccu); cu2[0] = 1; CHECK(refused(lim, e_ids.get(), cu2.data(), e_seq.get(), NC, "cu_cand")); }
+    { std::vector<int32_t> cu2(ccu); cu2[(size_t)NC] = cu2[(size_t)NC - 1]; CHECK(refused(lim, e_ids.get(), cu2.data(), e_seq.get(), NC, "cu_cand")); }
+    {
+      // one candidate of 17 tokens
+      std::vector<int32_t> ids2((size_t)kCandMaxLen + 1, 1);
+      const int32_t cu2[2] = {0, kCandMaxLen + 1}, seq2[1] = {0};
+      BatchLimits roomy = lim; roomy.Tmax = roomy.Smax = roomy.Rmax = std::max(big, 64); roomy.max_position = max_len + 64;
+      CHECK(refused(roomy, ids2.data(), cu2, seq2, 1, "TST_CAND_MAX_LEN"));
+      const int32_t cu3[2] = {0, kCandMaxLen};
+      err.clear();
+      CHECK(plan_candidates(&x.b, roomy, ids2.data(), cu3, seq2, 1, rr, err) == TST_OK);
+    }
+    { std::vector<int32_t> ids2(cids); ids2[(size_t)N - 1] = V; CHECK(refused(lim, ids2.data(), e_cu.get(), e_seq.get(), NC, "candidate id")); }
+    { std::vector<int32_t> ids2(cids); ids2[0] = -1; CHECK(refused(lim, ids2.data(), e_cu.get(), e_seq.get(), NC, "candidate id")); }
+    { std::vector<int32_t> seq2(cseq); seq2[(size_t)NC - 1] = S; CHECK(refused(lim, e_ids.get(), e_cu.get(), seq2.data(), NC, "cand_seq out of range")); }
+    { std::vector<int32_t> seq2(cseq); seq2[0] = -1; CHECK(refused(lim, e_ids.get(), e_cu.get(), seq2.data(), NC, "cand_seq out of range")); }
+    if (NC >= 2 && cseq[0] != cseq[(size_t)NC - 1]) {
+      std::vector<int32_t> seq2(cseq); std::swap(seq2[0], seq2[(size_t)NC - 1]);
+      CHECK(refused(lim, e_ids.get(), e_cu.get(), seq2.data(), NC, "non-decreasing"));
+    }
+    {
+      int need = 0;   // the largest len + L - 1 over the candidates
+      for (int c = 0; c < NC; ++c) need = std::max(need, x.cu[(size_t)cseq[(size_t)c] + 1] - x.cu[(size_t)cseq[(size_t)c]] + ccu[(size_t)c + 1] - ccu[(size_t)c] - 1);
+      int longest = 0;
+      for (int s = 0; s < S; ++s) longest = std::max(longest, x.cu[(size_t)s + 1] - x.cu[(size_t)s]);
+      BatchLimits shortpos = lim; shortpos.max_position = need - 1;
+      if (need - 1 >= longest) CHECK(refused(shortpos, e_ids.get(), e_cu.get(), e_seq.get(), NC, "exceeds max_position"));
+      shortpos.max_position = std::max(need, longest);
+      err.clear();
+      CHECK(plan_candidates(&x.b, shortpos, e_ids.get(), e_cu.get(), e_seq.get(), NC, rr, err) == TST_OK);
+    }
+    { BatchLimits few = lim; few.Rmax = N - 1; if (few.Rmax >= S) CHECK(refused(few, e_ids.get(), e_cu.get(), e_seq.get(), NC, "exceed max_labelled")); }
+    if (R >= 1) {
+      BatchLimits few = lim; few.Smax = R - 1;
+      if (few.Smax >= S) CHECK(refused(few, e_ids.get(), e_cu.get(), e_seq.get(), NC, "extend rows"));
+      few = lim; few.Tmax = R - 1;
+      if (few.Tmax >= T) CHECK(refused(few, e_ids.get(), e_cu.get(), e_seq.get(), NC, "extend rows"));
+    }
+    { BatchLimits few = lim; few.Rmax = S - 1; CHECK(refused(few, e_ids.get(), e_cu.get(), e_seq.get(), NC, "more sequences than max_labelled")); }
+  }
+}
+
 // token attribution: the row weights / kinds of plan_attribute, its refusals, and the un-trim of the fetch side
 static void test_attribute() {
   // three sequences of 1, 2 and 5 tokens; labels on the last token of the second and on the last three of the third
@@ -611,6 +730,7 @@ static void test_lora_layout() {
 int main() {
   test_plan_generate();
   test_plan_sample();
+  test_plan_candidates();
   test_attribute();
   test_ig();
   test_plan_batch();

@@ -206,6 +206,14 @@ template <typename AT> int attn_decode_shared(hipStream_t st, const AT* q, long 
 // d_ids[r] = tok, d_pos[r] = len + j, lab_idx[r] = r. ld a multiple of 4 and >= V rounded up to 4; the columns >= V are never candidates. Bit-reproducible.
 int sample_rows(hipStream_t st, const float* logits, long ld, int V, const int* geo, const int* seeds, int n_rows, int j, float inv_temp, int* tok, float* logp,
                 int* d_ids, int* d_pos, int* lab_idx);
+// decode.hip -- candidate scoring. geo = device ints {pre_row0, len, tail_row0, q_row0, n_pos} per candidate with at least two tokens (host_logic.h
+// plan_candidates). attn_extend: out[q_row0 + p, h dh ..] = attention of query row q_row0 + p over the keys 0 .. len + p (the prompt's rows, then the candidate's
+// own rows 0 .. p), p = 0 .. n_pos - 1, all candidates in one launch; per (p, h) bit-identical to attn_decode_shared at step = p + 1. n_rows = rows of q / out.
+template <typename AT> int attn_extend(hipStream_t st, const AT* q, long ldq, const AT* kcache, const AT* vcache, const int* geo, int n_cands, int n_rows, AT* out,
+                                       long ldo, int H, int Hkv, int dh, float scale, long cap_rows);
+// cand_logp: out[t] for the n candidate tokens, src = {row, tok} each. phase 0 writes the entries with tok >= 0 (a first token): logits[row, tok] - stats[row].lse;
+// phase 1 those with tok < 0: stats[row].logit[target] - stats[row].lse. stats = the {lse, logit[target], argmax, max} rows of logit_rows; n_rows = its rows.
+int cand_logp(hipStream_t st, const float* logits, long ld, int V, const float* stats, int n_rows, const int* src, int n, int phase, float* out);
 
 // One LoRA "module group" = adapters of linears that share an input (q,k,v | o | gate,up | down).
 template <typename AT>

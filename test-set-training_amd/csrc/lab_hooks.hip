@@ -499,6 +499,19 @@ int tst_k_sample_rows(const float* logits, int64_t ld, int V, const int32_t* geo
                       int32_t* d_ids, int32_t* d_pos, int32_t* lab_idx) {
   return sample_rows(nullptr, logits, (long)ld, V, geo, seeds, n_rows, j, inv_temp, tok, logp, d_ids, d_pos, lab_idx);
 }
+int tst_k_attn_extend(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* geo, int n_cands, int n_rows, void* out, int64_t ldo, int H,
+                      int Hkv, int dh, float scale, int64_t cap_rows) {
+  return attn_extend<bf16_t>(nullptr, (const bf16_t*)q, (long)ldq, (const bf16_t*)kcache, (const bf16_t*)vcache, geo, n_cands, n_rows, (bf16_t*)out, (long)ldo, H, Hkv,
+                             dh, scale, (long)cap_rows);
+}
+int tst_k_attn_extend_f32(const void* q, int64_t ldq, const void* kcache, const void* vcache, const int32_t* geo, int n_cands, int n_rows, void* out, int64_t ldo,
+                          int H, int Hkv, int dh, float scale, int64_t cap_rows) {
+  return attn_extend<float>(nullptr, (const float*)q, (long)ldq, (const float*)kcache, (const float*)vcache, geo, n_cands, n_rows, (float*)out, (long)ldo, H, Hkv, dh,
+                            scale, (long)cap_rows);
+}
+int tst_k_cand_logp(const float* logits, int64_t ld, int V, const float* stats, int n_rows, const int32_t* src, int n, int phase, float* out) {
+  return cand_logp(nullptr, logits, (long)ld, V, stats, n_rows, src, n, phase, out);
+}
 int tst_k_swiglu_fwd_f32(const void* gu, void* act, int T, int F) { return swiglu_fwd<float>(nullptr, (const float*)gu, (float*)act, T, F); }
 int tst_k_swiglu_bwd_f32(const void* dact, const void* gu, void* dgu, int T, int F) {
   return swiglu_bwd<float>(nullptr, (const float*)dact, (const float*)gu, (float*)dgu, T, F);

@@ -97,6 +97,11 @@ def build_parser():
         p.add_argument("--sample-seed", type=int, default=0, help="with --generate-samples: the run's seed; a QA pair's draws depend on it and the pair's id only")
         p.add_argument("--eos-ids", default=None, help="with --generate / --generate-samples: comma-separated token ids that end an answer; default: eos_token_id of "
                        "<model-dir>/generation_config.json or config.json when present, else none")
+        p.add_argument("--candidates", type=int, default=0, metavar="N", help="also score every held-out free-form (\"na\") sample's prompt against the N most "
+                       "frequent reference answers of the data set and its own (include/tst_hip.h tst_score_candidates_async: one prefill, every candidate "
+                       "token in one extend pass): the records gain cand = {n, rank and p_ref of the reference on that closed set, mass (log of the share of the "
+                       "model's distribution the list covers), top, top_p} and, with a tokenizer, top_text and mra_exp (expected mean relative accuracy without "
+                       "sampling noise). Independent of the other flags. 0: the run is unchanged")
         p.add_argument("--attribute", action="store_true", help="also attribute every held-out sample's score to its prompt tokens (one more forward + backward "
                        "per held-out batch; include/tst_hip.h tst_attribute_async): the records gain attr = {gxi, gnorm} over the prompt tokens and, with a "
                        "tokenizer, attr_top. Off: the run is unchanged. Not with --dp > 1 or --layout dp-stacked")
@@ -209,6 +214,11 @@ def _args_to_train(a):
         if not 0.01 <= t <= 100.0:   # (a NaN fails both)
             raise SystemExit("--temperature must lie in [0.01, 100]")
         gen.update(sample_n=n_smp, temperature=t, sample_seed=int(getattr(a, "sample_seed", 0) or 0), max_new_tokens=int(a.max_new_tokens), eos_ids=parse_eos_ids(a))
+    n_cand = int(getattr(a, "candidates", 0) or 0)
+    if n_cand != 0:
+        if not 1 <= n_cand <= 4096:
+            raise SystemExit("--candidates must be 1..4096 answers (0: off)")
+        gen.update(candidates=n_cand)
     if getattr(a, "attribute", False):
         if getattr(a, "dp", 1) > 1 or getattr(a, "layout", None) == "dp-stacked":
             raise SystemExit("--attribute is not available on the data-parallel layouts (--dp > 1, --layout dp-stacked)")
@@ -271,6 +281,13 @@ def _make_ctx(a, targs, local_rank, rank=0, world=1, max_answer=4):
     if gen_on and cfg.get("arch") == "gpt2" and a.max_len + targs.max_new_tokens > cfg["max_position"]:
         raise SystemExit(f"--generate / --generate-samples: --max-len {a.max_len} + --max-new-tokens {targs.max_new_tokens} exceeds the model's {cfg['max_position']} positions")
     draws = targs.per_device_eval_batch_size * S * targs.sample_n   # every draw of a held-out batch is a decode row and a head row (0 without --generate-samples)
+    if targs.candidates > 0:
+        # every candidate token of a held-out batch is a head row, all but the candidates' last tokens are token rows of the extend pass: N + 1 candidates of
+        # at most max_answer (<= TST_CAND_MAX_LEN) tokens per sample; room for a candidate behind the longest prompt (0 without --candidates)
+        draws = max(draws, targs.per_device_eval_batch_size * S * (targs.candidates + 1) * min(max(1, max_answer), lib.CAND_MAX_LEN))
+        L = max(L, max(128, a.max_len) + lib.CAND_MAX_LEN)
+        if cfg.get("arch") == "gpt2" and a.max_len + lib.CAND_MAX_LEN > cfg["max_position"]:
+            raise SystemExit(f"--candidates: --max-len {a.max_len} + {lib.CAND_MAX_LEN} candidate tokens exceeds the model's {cfg['max_position']} positions")
     ctx = lib.Context(cfg, device=local_rank, max_tokens=max(bs * L * S, draws), max_seqs=max(bs * S, draws), max_labelled=max(max(4, max_answer) * bs * S, draws),
                       max_position=min(L, cfg["max_position"]) if cfg.get("arch") == "gpt2" else L, lora_r=targs.lora_r,
                       lora_alpha=targs.lora_alpha, lora_targets=targs.lora_targets, beta1=targs.adam_beta1, beta2=targs.adam_beta2,
@@ -336,7 +353,7 @@ def main(argv=None):
         samples, opt_ids = TIO.load_qa_jsonl(a.data_file, tok, max_len=a.max_len)
         targs.option_ids = tuple(opt_ids)
     decode = None
-    if targs.generate or targs.attribute_ig > 0 or targs.sample_n > 0:
+    if targs.generate or targs.attribute_ig > 0 or targs.sample_n > 0 or targs.candidates > 0:
         tok_file = a.tokenizer or (os.path.join(a.model_dir, "tokenizer.json") if a.model_dir else None)
         if tok_file and os.path.exists(tok_file):
             from tokenizers import Tokenizer

@@ -18,6 +18,11 @@ With TrainArgs.attribute_ig > 0 every record also carries "attr_ig" = {"ig": [..
 the prompt tokens, walked from a prompt of TrainArgs.attribute_baseline_id tokens in attribute_ig steps (include/tst_hip.h tst_attribute_ig_async), log s of that
 baseline prompt, and the completeness gap sum(ig) - (log s - log s_base); with a `decode` function also "attr_ig_top": the attribute_top tokens of largest |ig| as
 [text, ig] pairs, signed. Not available on the data-parallel layouts either.
+With TrainArgs.candidates > 0 every "na" record also carries the model's exact distribution over the benchmark's own answers: "cand" = {"n": candidates scored (the
+TrainArgs.candidates most frequent reference answers of the data set and the record's own), "rank": of the reference among them (1 = the model's top answer),
+"p_ref": its probability on that closed set, "mass": log of the share of the model's whole distribution the list covers, "top" / "top_p": the five most probable
+candidates (token ids) and their probabilities} (include/tst_hip.h tst_score_candidates_async: one prefill per batch) and, with a `decode` function, "top_text" and
+-- where the reference answer reads as a number -- "mra_exp", the expected mean relative accuracy sum_c p_c MRA(text_c, reference), free of sampling noise.
 """
 import json
 import os
@@ -27,12 +32,14 @@ import time
 import numpy as np
 
 from . import kfold
-from .trainer import (ATTRIBUTE, GENERATE, IG, SAMPLE, SCORE, TrainArgs, fine_tune, fine_tune_concurrent, fine_tune_dp, fine_tune_stacked, run_heldout,
+from . import score as S
+from .trainer import (ATTRIBUTE, CANDIDATES, GENERATE, IG, SAMPLE, SCORE, TrainArgs, fine_tune, fine_tune_concurrent, fine_tune_dp, fine_tune_stacked, run_heldout,
                       run_heldout_concurrent, run_heldout_stacked)
 
 GEN_ARGS = ("generate", "max_new_tokens", "eos_ids")   # TrainArgs fields that enter the run fingerprint only when generation is on
 ATTR_ARGS = ("attribute", "attribute_top")             # TrainArgs settings that enter it only when attribution is on
 SAMPLE_ARGS = ("sample_n", "temperature", "sample_seed")   # likewise, when sampled answers are on (max_new_tokens / eos_ids then enter too: they shape the draws)
+CAND_ARGS = ("candidates",)                            # likewise, when candidate scoring is on
 IG_ARGS = ("attribute_ig", "attribute_baseline_id")    # likewise, when integrated gradients are on (attribute_top then enters too: it sizes attr_ig_top)
 
 
@@ -64,6 +71,12 @@ def run_fingerprint(samples, k, args, extra=None):
     else:
         for kk in SAMPLE_ARGS:
             a.pop(kk, None)
+    if int(getattr(args, "candidates", 0) or 0) > 0:
+        a.update({kk: getattr(args, kk) for kk in CAND_ARGS})
+    else:
+        for kk in CAND_ARGS:
+            a.pop(kk, None)
+    a.pop("candidate_list", None)   # (derived from the samples, which are hashed below)
     h.update(json.dumps(dict(args={kk: (list(v) if isinstance(v, tuple) else v) for kk, v in sorted(a.items())}, k=int(k), n=len(samples),
                              extra=extra or {}), sort_keys=True).encode())
     for x in samples:
@@ -112,20 +125,27 @@ def train_health(recs):
 
 
 def heldout_passes(layout, ctxs, helds, args: TrainArgs):
-    """score, then every enabled extra pass (generate, sample, attribute, ig: in this order) over the held-out folds. layout: "one" (ctxs is one context, helds one fold),
-    "concurrent" (a context per fold) or "stacked". Per fold: ((s, pred, correct), extras), extras = {"gen" / "samples" / "attr" / "ig": per-sample results} of what ran."""
+    """score, then every enabled extra pass (generate, sample, attribute, ig, candidates: in this order) over the held-out folds. layout: "one" (ctxs is one context, helds one fold),
+    "concurrent" (a context per fold) or "stacked". Per fold: ((s, pred, correct), extras), extras = {"gen" / "samples" / "attr" / "ig" / "cand": per-sample results} of what ran."""
     run = dict(one=lambda p, c, sets, a: [run_heldout(p, c, sets[0], a)], concurrent=run_heldout_concurrent, stacked=run_heldout_stacked)[layout]
     scored = run(SCORE, ctxs, helds, args)
     enabled = (("gen", GENERATE, args.generate), ("samples", SAMPLE, getattr(args, "sample_n", 0) > 0), ("attr", ATTRIBUTE, args.attribute),
-               ("ig", IG, args.attribute_ig > 0))
+               ("ig", IG, args.attribute_ig > 0), ("cand", CANDIDATES, getattr(args, "candidates", 0) > 0))
     ran = {key: run(p, ctxs, helds, args) for key, p, on in enabled if on}
     return [(sc, {key: got[i] for key, got in ran.items()}) for i, sc in enumerate(scored)]
 
 
-def fold_records(held, f, rnd, s, pred, correct, decode=None, attr_top=5, *, gen=None, attr=None, ig=None, samples=None):
+def set_candidates(samples, args):
+    """the data set's candidate answers (tst.score.answer_candidates over ALL samples, held-out ones included: the list is the benchmark's answer vocabulary, not
+    something learned) on args.candidate_list, once per run, when candidate scoring is on"""
+    if int(getattr(args, "candidates", 0) or 0) > 0 and getattr(args, "candidate_list", None) is None:
+        args.candidate_list = S.answer_candidates(samples, args.candidates)
+
+
+def fold_records(held, f, rnd, s, pred, correct, decode=None, attr_top=5, *, gen=None, attr=None, ig=None, samples=None, cand=None):
     """the records of one scored held-out fold; decode = ids -> text; the extras (heldout_passes' mapping, as keywords): gen = [(gen ids, gen_correct)] per sample
     when generation is on, samples = tst.score.sampled_answers' dict when sampled answers are, attr = tst.score.token_attribution's dict when attribution is on,
-    ig = tst.score.token_ig's when integrated gradients are"""
+    ig = tst.score.token_ig's when integrated gradients are, cand = tst.score.candidate_scores' (None for the samples without candidates) when candidate scoring is"""
     records = [dict(id=int(x.sid), fold=int(f), round=int(rnd), s=float(si), pred=int(pi), correct=int(ci), kind=x.kind)
                for x, si, pi, ci in zip(held, s, pred, correct)]
     if gen is not None:
@@ -158,6 +178,18 @@ def fold_records(held, f, rnd, s, pred, correct, decode=None, attr_top=5, *, gen
             if decode is not None:
                 top = np.argsort(-np.abs(np.asarray(a["ig"], np.float64)), kind="stable")[:max(0, int(attr_top))]
                 r["attr_ig_top"] = [[decode([int(x.ids[t])]), float(a["ig"][t])] for t in top]
+    if cand is not None:
+        from .benchmarks import mean_relative_accuracy, parse_number
+        for r, x, c in zip(records, held, cand):
+            if c is None:   # "mca": its restricted softmax over the option letters already is this
+                continue
+            r["cand"] = dict(n=int(c["n"]), rank=c["rank"], p_ref=c["p_ref"], mass=float(c["mass"]), top=[[int(t) for t in g] for g in c["top"]],
+                             top_p=[float(v) for v in c["top_p"]])
+            if decode is not None:
+                r["cand"]["top_text"] = [decode(g) for g in r["cand"]["top"]]
+                ref = decode([int(t) for t in x.ids[x.n_prompt:]])
+                if parse_number(ref) is not None:
+                    r["cand"]["mra_exp"] = float(sum(float(pc) * mean_relative_accuracy(decode([int(t) for t in g]), ref) for pc, g in zip(c["p"], c["cands"])))
     return records
 
 
@@ -229,6 +261,7 @@ def diagnose(ctx, samples, k, args: TrainArgs, rank=0, world=1, rnd=0, out_dir=N
     about model / weights / data (any JSON-able dict); it goes into the run fingerprint that guards resume. `decode` (ids -> text): with args.generate the
     records also carry "gen_text"."""
     assign = kfold.kfold_assign(len(samples), k, True, args.seed)
+    set_candidates(samples, args)
     if out_dir and resume:
         check_fingerprint(out_dir, rnd, run_fingerprint(samples, k, args, identity), rank)
     records, stats, todo = [], [], []
@@ -264,6 +297,7 @@ def diagnose_dp(ctx, samples, k, args: TrainArgs, rank, world, dp, rnd=0, out_di
         raise ValueError("token attribution is not available on data-parallel contexts (include/tst_hip.h tst_attribute_async)")
     g, n_groups, dp_rank, _ = ddp.dp_layout(rank, world, dp)
     assign = kfold.kfold_assign(len(samples), k, True, args.seed)
+    set_candidates(samples, args)
     if out_dir and resume:
         check_fingerprint(out_dir, rnd, run_fingerprint(samples, k, args, identity), rank)
     records, stats = [], []
@@ -304,6 +338,7 @@ def diagnose_dp_stacked(ctxs, samples, k, args: TrainArgs, rank, world, rnd=0, o
         raise ValueError("token attribution is not available on data-parallel contexts (include/tst_hip.h tst_attribute_async)")
     cap = sum(getattr(c, "n_stack", 1) for c in group)
     assign = kfold.kfold_assign(len(samples), k, True, args.seed)
+    set_candidates(samples, args)
     if out_dir and resume:
         check_fingerprint(out_dir, rnd, run_fingerprint(samples, k, args, dict(identity or {}, layout="dp-stacked", world=world)), rank)
     if gather is None and out_dir:

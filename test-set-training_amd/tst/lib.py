@@ -138,6 +138,9 @@ SIGNATURES = {
     "tst_sample_async": (C.c_int, [_P, C.POINTER(Batch), C.c_int32, C.c_int32, _F, _P, _P, C.c_int32]),
     "tst_sample_fetch": (C.c_int, [_P, _P, _P, _P]),
     "tst_sample": (C.c_int, [_P, C.POINTER(Batch), C.c_int32, C.c_int32, _F, _P, _P, C.c_int32, _P, _P, _P]),
+    "tst_score_candidates_async": (C.c_int, [_P, C.POINTER(Batch), _P, _P, _P, C.c_int32]),
+    "tst_score_candidates_fetch": (C.c_int, [_P, _P, _P]),
+    "tst_score_candidates": (C.c_int, [_P, C.POINTER(Batch), _P, _P, _P, C.c_int32, _P, _P]),
     "tst_attribute_async": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.c_int32]),
     "tst_attribute_fetch": (C.c_int, [_P, _P, _P, _P]),
     "tst_attribute": (C.c_int, [_P, C.POINTER(Batch), _P, _P, C.c_int32, _P, _P, _P]),
@@ -202,6 +205,9 @@ LAB_SIGNATURES = {
     "tst_k_attn_decode_shared": (C.c_int, [_P, _L, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _F, _L]),
     "tst_k_attn_decode_shared_f32": (C.c_int, [_P, _L, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _F, _L]),
     "tst_k_sample_rows": (C.c_int, [_P, _L, _I, _P, _P, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "tst_k_attn_extend": (C.c_int, [_P, _L, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _F, _L]),
+    "tst_k_attn_extend_f32": (C.c_int, [_P, _L, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _F, _L]),
+    "tst_k_cand_logp": (C.c_int, [_P, _L, _I, _P, _I, _P, _I, _I, _P]),
     "tst_k_kv_append_f32": (C.c_int, [_P, _L, _I, _P, _P, _P, _I, _I, _I, _L]),
     "tst_k_attn_decode_f32": (C.c_int, [_P, _L, _P, _P, _P, _I, _I, _P, _L, _I, _I, _I, _F, _L]),
     "tst_k_adamw": (C.c_int, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _I, _P, _P]),
@@ -244,6 +250,7 @@ HOST_SIGNATURES = {
     "tst_host_plan_batch": (C.c_int, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _I]),
     "tst_host_plan_generate": (C.c_int, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I]),
     "tst_host_plan_sample": (C.c_int, [_P, _P, _I, _I, _F, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I]),
+    "tst_host_plan_candidates": (C.c_int, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "tst_host_cut_at_eos": (C.c_int, [_P, _P, _P, _I, _I, _P, _I]),
     "tst_host_plan_attribute": (C.c_int, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I]),
     "tst_host_untrim_tokens": (C.c_int, [_P, _P, _P, _I, _P]),
@@ -428,6 +435,48 @@ def host_plan_sample(mc, ids, cu, max_new, n_samples, temperature, seq_seeds, eo
     return dict(S=int(out[0]), T=int(out[1]), R=R, rows_used=int(out[3]), cache_rows=int(out[4]), dev_ints=int(out[5]), dev_ints_alloc=int(out[6]),
                 slot_r_end=out[7:15].astype(np.int32), geo=geo[:3 + 3 * R], seeds=seeds[:2 * S].reshape(S, 2), last_rows=last[:S], prefill_rows=pre[:T],
                 decode_rows=dec[:(int(max_new) - 1) * R].reshape(int(max_new) - 1, R))
+
+
+CAND_MAX_LEN = 16   # TST_CAND_MAX_LEN
+
+
+def pack_candidates(cands, cand_seq):
+    """(cand_ids, cu_cand, cand_seq) int32 arrays of a list of token-id sequences and the prompt index each continues"""
+    cu = np.zeros(len(cands) + 1, np.int32)
+    for i, c in enumerate(cands):
+        cu[i + 1] = cu[i] + len(c)
+    ids = np.array([t for c in cands for t in c], np.int32)
+    return ids, cu, np.ascontiguousarray(cand_seq, np.int32)
+
+
+def host_plan_candidates(mc, ids, cu, cand_ids, cu_cand, cand_seq, seq_slot=None):
+    """tsthost::plan_candidates through the CPU library: dict(S, T, n_tok, R_e, n_ext, rows_used, cache_rows, dev_ints, slot_r_end, geo [n_ext, 5], ext_rows,
+    ext_ids, ext_pos, ext_tgt [R_e], src [n_tok, 2], last_rows [S]); raises TstError with the library's message for a refused call"""
+    L = load_host()
+    ids = np.ascontiguousarray(ids, np.int32)
+    cu = np.ascontiguousarray(cu, np.int32)
+    sl = None if seq_slot is None else np.ascontiguousarray(seq_slot, np.int32)
+    ip = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+    S, T = len(cu) - 1, len(ids)
+    b = Batch(ip(ids), None, ip(cu), S, T, ip(sl), 0)
+    cand_ids = np.ascontiguousarray(cand_ids, np.int32)
+    cu_cand = np.ascontiguousarray(cu_cand, np.int32)
+    cand_seq = np.ascontiguousarray(cand_seq, np.int32)
+    n_cands = len(cu_cand) - 1
+    if len(cand_seq) != max(n_cands, 0) or (n_cands >= 1 and len(cand_ids) < int(cu_cand.max())):
+        raise TstError("cand_seq needs one entry per candidate and cand_ids cu_cand[-1] tokens")
+    n = max(len(cand_ids), 1)
+    out, err = np.zeros(16, np.int64), C.create_string_buffer(256)
+    geo, rows, eid, epos, etgt = (np.zeros(5 * n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32))
+    src, last = np.zeros(2 * n, np.int32), np.zeros(max(S, 1), np.int32)
+    rc = L.tst_host_plan_candidates(C.byref(mc), C.byref(b), _ptr(cand_ids) if len(cand_ids) else None, _ptr(cu_cand), _ptr(cand_seq) if n_cands > 0 else None,
+                                    int(n_cands), _ptr(out), _ptr(geo), _ptr(rows), _ptr(eid), _ptr(epos), _ptr(etgt), _ptr(src), _ptr(last), err, 256)
+    if rc != 0:
+        raise TstError(err.value.decode() or f"tst_host_plan_candidates rc={rc}")
+    n_tok, R, n_ext = int(out[2]), int(out[3]), int(out[4])
+    return dict(S=int(out[0]), T=int(out[1]), n_tok=n_tok, R_e=R, n_ext=n_ext, rows_used=int(out[5]), cache_rows=int(out[6]), dev_ints=int(out[7]),
+                slot_r_end=out[8:16].astype(np.int32), geo=geo[:5 * n_ext].reshape(n_ext, 5), ext_rows=rows[:R], ext_ids=eid[:R], ext_pos=epos[:R], ext_tgt=etgt[:R],
+                src=src[:2 * n_tok].reshape(n_tok, 2), last_rows=last[:S])
 
 
 def host_cut_at_eos(tokens, logp, eos_ids):
@@ -1040,6 +1089,36 @@ class Context:
     def sample(self, ids, cu, max_new_tokens, n_samples, temperature, seq_seeds, eos_ids=(), seq_slot=None):
         self.sample_async(ids, cu, max_new_tokens, n_samples, temperature, seq_seeds, eos_ids, seq_slot)
         return self.sample_fetch()
+
+    # ---- candidate scoring (include/tst_hip.h tst_score_candidates_async)
+    def score_candidates_async(self, ids, cu, cand_ids, cu_cand, cand_seq, seq_slot=None):
+        """enqueue the exact log p(candidate | prompt) of the packed candidates (cand_ids, cu_cand; candidate c continues prompt cand_seq[c], non-decreasing) of
+        the packed prompts (ids, cu), at one prefill. Results come from score_candidates_fetch()."""
+        b, keep = self._batch(ids, None, cu, seq_slot)
+        cu_c = np.ascontiguousarray(cu_cand, np.int32).reshape(-1)
+        seq_c = np.ascontiguousarray(cand_seq, np.int32).reshape(-1)
+        ids_c = np.ascontiguousarray(cand_ids, np.int32).reshape(-1)
+        n_cands = len(cu_c) - 1
+        if n_cands < 0 or len(seq_c) != n_cands or (n_cands >= 1 and len(ids_c) < int(cu_c.max())):
+            raise TstError("cand_seq needs one entry per candidate and cand_ids cu_cand[-1] tokens")
+        if len(ids_c) == 0:
+            ids_c = np.zeros(1, np.int32)
+        if len(seq_c) == 0:
+            seq_c = np.zeros(1, np.int32)
+        self._check(self.lib.tst_score_candidates_async(self.h, C.byref(b), _ptr(ids_c), _ptr(cu_c), _ptr(seq_c), n_cands), "tst_score_candidates_async")
+        self._pending_cand = (int(cu_c[-1]), n_cands)
+
+    def score_candidates_fetch(self):
+        """(logp_tok [n_cand_tokens], logp_cand [n_cands]): the teacher-forced log-probability of every candidate token and their sum per candidate"""
+        n_tok, n_c = getattr(self, "_pending_cand", None) or (1, 1)
+        lt, lc = np.zeros(max(n_tok, 1), np.float32), np.zeros(max(n_c, 1), np.float32)
+        self._check(self.lib.tst_score_candidates_fetch(self.h, _ptr(lt), _ptr(lc)), "tst_score_candidates_fetch")
+        self._pending_cand = None
+        return lt[:n_tok], lc[:n_c]
+
+    def score_candidates(self, ids, cu, cand_ids, cu_cand, cand_seq, seq_slot=None):
+        self.score_candidates_async(ids, cu, cand_ids, cu_cand, cand_seq, seq_slot)
+        return self.score_candidates_fetch()
 
     # ---- token attribution (include/tst_hip.h tst_attribute_async)
     def attribute_async(self, ids, labels, cu, seq_kind=None, option_ids=(), seq_slot=None):

@@ -142,3 +142,73 @@ def sampled_answers(samples, tokens, logp, n_new, eos_ids=()):
             hit += int(len(ans) > 0 and gen[:len(ans)] == ans)
         out.append(dict(ids=ids, logp=lps, match=hit / max(len(ids), 1)))
     return out
+
+
+CAND_MAX_LEN = 16   # TST_CAND_MAX_LEN (include/tst_hip.h): a longer answer is not a candidate
+
+
+def answer_candidates(samples, top):
+    """the `top` most frequent distinct reference answers (token-id tuples, ids[n_prompt:]) over the "na" samples of the whole data set, most frequent first; ties
+    go to the answer that occurs first. Answers of more than CAND_MAX_LEN tokens (or none) are left out: tst_score_candidates_async does not take them."""
+    count, first = {}, {}
+    for i, x in enumerate(samples):
+        if x.kind != "na":
+            continue
+        ans = tuple(int(t) for t in x.ids[x.n_prompt:])
+        if not 1 <= len(ans) <= CAND_MAX_LEN:
+            continue
+        count[ans] = count.get(ans, 0) + 1
+        first.setdefault(ans, i)
+    return sorted(count, key=lambda a: (-count[a], first[a]))[:max(0, int(top))]
+
+
+def sample_candidates(x, cands):
+    """the candidates one held-out sample is scored on: none for an "mca" sample (its restricted softmax already is this); for an "na" sample the data set's list
+    `cands` and, behind it, the sample's own reference answer when the list does not hold it (and it has 1 .. CAND_MAX_LEN tokens)"""
+    if x.kind != "na":
+        return []
+    out = [tuple(c) for c in cands]
+    ref = tuple(int(t) for t in x.ids[x.n_prompt:])
+    if ref not in out and 1 <= len(ref) <= CAND_MAX_LEN:
+        out.append(ref)
+    return out
+
+
+def pack_candidates(samples, cands):
+    """(cand_ids, cu_cand, cand_seq) of a held-out batch for Context.score_candidates: sample_candidates of every sample, in batch order"""
+    ids, cu, seq = [], [0], []
+    for s, x in enumerate(samples):
+        for c in sample_candidates(x, cands):
+            ids += list(c)
+            cu.append(len(ids))
+            seq.append(s)
+    return np.array(ids, np.int32), np.array(cu, np.int32), np.array(seq, np.int32)
+
+
+def candidate_scores(samples, cands, logp_cand):
+    """samples: a held-out batch in the order of pack_candidates(samples, cands); logp_cand: log p(candidate | prompt) of its candidates, flat, as
+    Context.score_candidates_fetch returns them. Per sample None ("mca", or no candidate at all) or dict(n = candidates scored, cands = their id tuples,
+    logp = their log-probabilities, p = softmax(logp) over the sample's list (float64), mass = logsumexp(logp): the share of the model's own distribution the list
+    covers (as a log), rank = 1 + the number of candidates strictly more probable than the reference (None when the reference is not on the list), p_ref = the
+    reference's p (None likewise), top / top_p = the five most probable candidates and their p, ties in list order)."""
+    lp_all = np.asarray(logp_cand, np.float64).reshape(-1)
+    n_all = sum(len(sample_candidates(x, cands)) for x in samples)
+    if n_all != len(lp_all):
+        raise ValueError(f"candidate_scores: {len(lp_all)} log-probabilities for {n_all} candidates")
+    out, o = [], 0
+    for x in samples:
+        mine = sample_candidates(x, cands)
+        if not mine:
+            out.append(None)
+            continue
+        lp = lp_all[o:o + len(mine)]
+        o += len(mine)
+        m = float(lp.max())
+        mass = m + float(np.log(np.exp(lp - m).sum()))
+        p = np.exp(lp - mass)
+        ref = tuple(int(t) for t in x.ids[x.n_prompt:])
+        j = mine.index(ref) if ref in mine else None
+        order = np.argsort(-lp, kind="stable")[:5]
+        out.append(dict(n=len(mine), cands=mine, logp=lp.copy(), p=p, mass=mass, rank=None if j is None else 1 + int((lp > lp[j]).sum()),
+                        p_ref=None if j is None else float(p[j]), top=[list(mine[k]) for k in order], top_p=[float(p[k]) for k in order]))
+    return out

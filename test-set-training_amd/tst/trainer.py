@@ -56,8 +56,13 @@ class TrainArgs:
     sample_n: InitVar[int] = 0
     temperature: InitVar[float] = 1.0
     sample_seed: InitVar[int] = 0
+    # candidate-answer scoring on the held-out fold (off at 0): every "na" record gains `cand`, the model's exact distribution over the `candidates` most frequent
+    # reference answers of the data set plus the record's own (include/tst_hip.h tst_score_candidates_async; tst.score.answer_candidates / candidate_scores).
+    # candidate_list is that list: tst.diagnose fills it from the whole data set before the first fold. Attributes, NOT dataclass fields, for the reason above.
+    candidates: InitVar[int] = 0
 
-    def __post_init__(self, attribute, attribute_top, attribute_ig, attribute_baseline_id, sample_n, temperature, sample_seed):
+    def __post_init__(self, attribute, attribute_top, attribute_ig, attribute_baseline_id, sample_n, temperature, sample_seed, candidates):
+        self.candidates, self.candidate_list = int(candidates), None
         self.attribute, self.attribute_top = bool(attribute), int(attribute_top)
         self.attribute_ig, self.attribute_baseline_id = int(attribute_ig), int(attribute_baseline_id)
         self.sample_n, self.temperature, self.sample_seed = int(sample_n), float(temperature), int(sample_seed)
@@ -225,6 +230,22 @@ def _sample_fetch(ctx, batch, args):
     return S.sampled_answers(batch, tok, logp, n_new, args.eos_ids)
 
 
+def _candidates_enqueue(ctx, batch, args, *seq_slot):
+    if args.candidate_list is None:
+        raise ValueError("TrainArgs.candidate_list is not set: tst.score.answer_candidates(samples, args.candidates) over the whole data set")
+    cand_ids, cu_cand, cand_seq = S.pack_candidates(batch, args.candidate_list)
+    if len(cand_seq):   # (a batch of "mca" samples only has nothing to score)
+        ids, cu = collate_prompts(batch)
+        ctx.score_candidates_async(ids, cu, cand_ids, cu_cand, cand_seq, *seq_slot)
+
+
+def _candidates_fetch(ctx, batch, args):
+    if not any(S.sample_candidates(x, args.candidate_list) for x in batch):
+        return [None] * len(batch)
+    _, logp_cand = ctx.score_candidates_fetch()
+    return S.candidate_scores(batch, args.candidate_list, logp_cand)
+
+
 def _attribute_enqueue(ctx, batch, args, *seq_slot):
     ids, labels, cu = D.collate(batch)
     ctx.attribute_async(ids, labels, cu, S.attribution_kinds(batch), args.option_ids, *seq_slot)   # MCA and open samples in one batch
@@ -243,6 +264,9 @@ GENERATE = HeldoutPass(_generate_enqueue, _generate_fetch, list)
 # args.sample_n draws per prompt from softmax(logits / args.temperature), one prefill per batch: tst.score.sampled_answers' dict per sample. A pair's draws depend
 # on args.sample_seed and its id only, not on the fold layout, the batch or the slot
 SAMPLE = HeldoutPass(_sample_enqueue, _sample_fetch, list)
+# exact log p(candidate | prompt) over args.candidate_list (+ the sample's own reference) for every "na" sample, one prefill per batch:
+# tst.score.candidate_scores' dict per sample (None for "mca")
+CANDIDATES = HeldoutPass(_candidates_enqueue, _candidates_fetch, list)
 # input-gradient attribution of log s(x): tst.score.token_attribution's dict per sample. About one training forward + backward per batch.
 ATTRIBUTE = HeldoutPass(_attribute_enqueue, lambda ctx, batch, args: S.token_attribution(batch, *ctx.attribute_fetch()), list)
 # integrated gradients of log s(x), args.attribute_ig steps from a prompt of args.attribute_baseline_id: tst.score.token_ig's dict per sample.
@@ -332,6 +356,11 @@ def generate_heldout(ctx, samples, args: TrainArgs):
 def sample_heldout(ctx, samples, args: TrainArgs):
     """args.sample_n sampled continuations of every held-out prompt; returns tst.score.sampled_answers' dict per sample in input order."""
     return run_heldout(SAMPLE, ctx, samples, args)
+
+
+def candidates_heldout(ctx, samples, args: TrainArgs):
+    """the model's distribution over the candidate answers for every held-out "na" sample; returns tst.score.candidate_scores' dict (None for "mca") per sample."""
+    return run_heldout(CANDIDATES, ctx, samples, args)
 
 
 def attribute_heldout(ctx, samples, args: TrainArgs):

@@ -17,9 +17,10 @@ run() {
 }
 : > gpurun_out/ci.log
 TMO=${TMO:-420}
-run kernels python -m pytest tests/test_kernels_gpu.py tests/test_kernels_gpt2_gpu.py tests/test_attention_long_gpu.py tests/test_head_norm_gpu.py tests/test_decode_kernels_gpu.py tests/test_sample_kernels_gpu.py tests/test_optim_kernels_gpu.py -q -m gpu -p no:cacheprovider
+run kernels python -m pytest tests/test_kernels_gpu.py tests/test_kernels_gpt2_gpu.py tests/test_attention_long_gpu.py tests/test_head_norm_gpu.py tests/test_decode_kernels_gpu.py tests/test_sample_kernels_gpu.py tests/test_candidate_kernels_gpu.py tests/test_optim_kernels_gpu.py -q -m gpu -p no:cacheprovider
 run engine python -m pytest tests/test_engine_gpu.py tests/test_stacked_gpu.py tests/test_full_finetune_gpu.py tests/test_ddp_gpu.py tests/test_io_gpu.py tests/test_edge_cases_gpu.py tests/test_diagnostic_gpu.py tests/test_torch_coexist_gpu.py tests/test_agreement_gpu.py tests/test_zero_gpu.py tests/test_long_sequences_gpu.py tests/test_generate_gpu.py tests/test_tensor_names_gpu.py tests/test_heldout_gpu.py tests/test_create_gpu.py -q -m gpu -p no:cacheprovider
 run sample python -m pytest tests/test_sample_gpu.py -q -m gpu -p no:cacheprovider
+run candidates python -m pytest tests/test_candidates_gpu.py -q -m gpu -p no:cacheprovider
 run qwen3 python -m pytest tests/test_qwen3_gpu.py -q -m gpu -p no:cacheprovider
 run attribution python -m pytest tests/test_attribution_gpu.py -q -m gpu -p no:cacheprovider
 run ig python -m pytest tests/test_ig_gpu.py -q -m gpu -p no:cacheprovider
